@@ -5,14 +5,19 @@ A step = one depth frame taken through SDF_Hashtable::integrate (lock epoch -> a
 flattenIntoBuffer -> integrateDepthMap) on the synthetic room of config C2 (640x480); vertex maps
 and poses are resident in HBM before the timed region.  One JSON line on stdout (rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C5] [--legs a,b,...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C5] [--dump-outputs DIR]
+                  [--full [--legs a,b,...]]
 
-Timing: after a fixed run-in lap and W warm-up steps, windows of EXACTLY K steps are timed, each
-bracketed by a barrier and a device synchronisation on both sides; windows are repeated until at
-least one second (comparison legs: MIN_TIMED_S) has been timed and `value` is K * frames_per_step /
-(median window).  Everything else
-in the line (roofline, first lap, C3 sub-record, loaded integrate, raycast, sharded path with one
-rank, CPU baseline) is measured after that, outside the timed windows.
+Timing (one GPU, the default): after a fixed run-in lap and W warm-up steps, ONE window of exactly K
+steps is timed, bracketed by a device synchronisation on both sides; `value` is K * frames_per_step /
+(window) and `ms_per_step` the window / K.  --dump-outputs DIR then writes the model those steps left
+(dump_outputs()).  A plain run stops there.  With --full the headline is the same single window (with a
+small K a few milliseconds; earlier rounds took the median of windows repeated for a second), and
+everything else in the line (roofline, first lap, C3 sub-record, loaded integrate, raycast, sharded path
+with one rank, CPU baseline) is measured after it, outside the timed window; its comparison legs repeat
+their windows until MIN_TIMED_S (or a second) has been timed.
+The bucket-range-sharded path (--gpus N > 1, --sharded: voxelhashing_demo_amd/dist.py bench_sharded) keeps
+its own rule: windows of K steps repeated until about 0.3 s has been timed, `value` on the median window.
 """
 from __future__ import annotations
 
@@ -78,9 +83,14 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--frames", type=int, default=0, help="distinct resident frames (default: workload's)")
-    ap.add_argument("--legs", default="all",
-                    help="comma list of the extra legs to run after the timed windows: " + ",".join(ALL_LEGS) +
-                         " (all / none); the timed windows and the roofline of the dominant kernel always run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window, also measure the roofline of the dominant kernel and the extra legs "
+                         "(--legs); a plain run times the headline window only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the model they left as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--legs", default=None,
+                    help="with --full: comma list of the extra legs to run after the timed window: " + ",".join(ALL_LEGS) +
+                         " (all / none; default all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames in the CPU sample (0 = auto, about 15 s)")
     ap.add_argument("--raycast-steps", type=int, default=50)
@@ -101,7 +111,12 @@ def parse_args():
     ap.add_argument("--sharded", action="store_true",
                     help="force the bucket-range-sharded path (torch.distributed) even with one rank")
     a = ap.parse_args()
-    legs = set(ALL_LEGS) if a.legs == "all" else set() if a.legs == "none" else set(a.legs.split(","))
+    if a.legs not in (None, "none") and not a.full:
+        ap.error("--legs selects the extra legs of --full; add --full")
+    if a.dump_outputs and (a.gpus > 1 or a.sharded):
+        ap.error("--dump-outputs writes the model of the one-GPU path (--gpus 1, not --sharded)")
+    a.legs = "all" if a.legs is None else a.legs
+    legs = set() if not a.full else set(ALL_LEGS) if a.legs == "all" else set() if a.legs == "none" else set(a.legs.split(","))
     if legs - set(ALL_LEGS):
         ap.error("--legs: unknown leg(s) " + ",".join(sorted(legs - set(ALL_LEGS))) + "; known: " + ",".join(ALL_LEGS))
     if a.no_cpu_baseline:
@@ -360,8 +375,10 @@ class Integrator:
 
 
 def measure_workload(args, V, L, synth, torch, name, local_rank, steps, warmup, want_profile=True, frames=None,
-                     pipeline=True):
-    """Timed windows + dominant-kernel roofline of one single-GPU workload.  Returns (record, Integrator, poses, verts)."""
+                     pipeline=True, headline=False):
+    """Timed windows + dominant-kernel roofline of one single-GPU workload.  Returns (record, Integrator, poses, verts).
+    headline: the line's own measurement -- exactly one window of `steps` steps, then --dump-outputs; without --full nothing
+    more (no occupancy pass, no profile pass, no byte counts)."""
     wl = dict(WORKLOADS[name], options=list(WORKLOADS[name].get("options", [])) + list(getattr(args, "option", [])))
     dev = torch.device("cuda", local_rank)
     stream = torch.cuda.Stream(device=dev)
@@ -374,14 +391,20 @@ def measure_workload(args, V, L, synth, torch, name, local_rank, steps, warmup, 
     for i in range(lap):           # fixed, untimed run-in (one lap of the resident frames) before the W warm-up steps
         it.step(i)
     it.sync()
-    # (the headline windows are repeated until a full second has been timed; the comparison legs settle for 0.3 s)
+    # (the headline is one window of exactly K steps; the workloads of the comparison legs repeat theirs until a full second
+    # has been timed, the other legs settle for 0.3 s)
     times, nxt = timed_windows(it.step, lambda: (it.sync(), torch.cuda.synchronize()), steps, warmup, first=lap,
-                               min_time=1.0)
+                               min_time=0.0 if headline else 1.0)
     rec = window_stats(times, steps, B)
+    rec["ms_per_frame"] = round(rec["ms_per_step"] / B, 5)
     counters = it.table.counters()
     if counters["spin_timeouts"]:          # (a serialised launch gave up waiting: the frames timed are not the frames fused)
         raise SystemExit(f"bench.py: {counters['spin_timeouts']} workgroups of serialised launches timed out (vh_counters.spin_timeouts)")
     rec["occupied_blocks_last_frame"], rec["allocated_blocks"], rec["resident_frames"] = counters["occupied"], counters["allocated_total"], nframes
+    if headline and args.dump_outputs:
+        rec["outputs"] = dump_outputs(args.dump_outputs, it.table)
+    if headline and not args.full:
+        return rec, it, poses, verts
     # the visible-block count the byte formulas use is the MEAN over the resident frames (the counter passes and the per-dispatch
     # times are means over all of them too; the last frame's count alone made the walk-free frame's traffic look 1.4 x its bytes)
     occ = it.mean_occupied()
@@ -400,10 +423,53 @@ def measure_workload(args, V, L, synth, torch, name, local_rank, steps, warmup, 
     rec["frame_algorithmic_bytes"] = b_frame
     rec["input"] = ("uint16 sensor images (vh_integrate_depth_batch): input terms 2*W*H + 2*W*H in place of 16*W*H + 4*W*H"
                     if it.sensor else "float4 vertex maps (vh_integrate_batch)")
-    rec["ms_per_frame"] = round(rec["ms_per_step"] / B, 5)
     rec["frame_algorithmic_gbs"] = round(b_frame * rec["value"] / 1e9, 1)
     rec["frame_frac_of_hbm_peak"] = round(b_frame * rec["value"] / 1e9 / HBM_PEAK_GBS, 4)
     return rec, it, poses, verts
+
+
+DUMP_VOXEL_BLOCKS = 4096        # --dump-outputs: voxels of at most this many blocks (16 MB; a seeded sample beyond it) ...
+DUMP_POS_ROWS = 1 << 20          # ... and at most this many rows (12 MB) per list of block positions
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, table):
+    """What the timed steps computed: the model vh_integrate_batch leaves behind, as a caller reads it back, in an order that
+    does not depend on which thread won an allocation (blocks sorted by position; a block's heap slot is not written).
+      blocks_pos.npy      [n, 3] float32    every allocated block's integer position, sorted
+      visible_pos.npy     [m, 3] float32    the blocks of the last frame (the compact list), sorted
+      voxels_pos.npy      [k, 3] float32    the blocks whose voxels follow, sorted
+      voxels_sdf.npy      [k, 512] float32  their TSDF, voxels_weight.npy [k, 512] float32 their weights
+    A list longer than its cap (DUMP_POS_ROWS, DUMP_VOXEL_BLOCKS) is a fixed seeded sample of its sorted rows, so that the
+    files stay below 64 MB in all.  Returns {name: shape}."""
+    from voxelhashing_demo_amd import _lib as L
+    os.makedirs(out_dir, exist_ok=True)
+    table.synchronize()
+
+    def sorted_rows(entries, cap):
+        pos = np.asarray(entries["pos"], np.int64).reshape(-1, 3)
+        rows = entries[np.lexsort((pos[:, 2], pos[:, 1], pos[:, 0]))]
+        if len(rows) > cap:
+            rows = rows[np.sort(np.random.default_rng(DUMP_SEED).choice(len(rows), cap, replace=False))]
+        return rows
+
+    def pos32(rows):
+        return np.asarray(rows["pos"], np.float32).reshape(-1, 3)
+
+    ht = table.hash_table()
+    alloc = ht[ht["ptr"] != L.FREE_BLOCK]
+    sampled = sorted_rows(alloc, DUMP_VOXEL_BLOCKS)
+    sdf = np.empty((len(sampled), 512), np.float32)
+    weight = np.empty((len(sampled), 512), np.float32)
+    for j, e in enumerate(sampled):
+        v = table.block_voxels(int(e["ptr"]))
+        sdf[j], weight[j] = v["sdf"], v["weight"]
+    arrays = dict(blocks_pos=pos32(sorted_rows(alloc, DUMP_POS_ROWS)),
+                  visible_pos=pos32(sorted_rows(table.compact(), DUMP_POS_ROWS)),
+                  voxels_pos=pos32(sampled), voxels_sdf=sdf, voxels_weight=weight)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def two_launch_record(args, it, name, occ, steps, warmup, sync):
@@ -682,12 +748,13 @@ def main():
     name = args.workload
     wl = WORKLOADS[name]
     Wd, Ht = wl["width"], wl["height"]
-    main_rec, it, poses, verts = measure_workload(args, V, L, synth, torch, name, local_rank, args.steps, args.warmup)
+    main_rec, it, poses, verts = measure_workload(args, V, L, synth, torch, name, local_rank, args.steps, args.warmup,
+                                                  headline=True)
     table, lib, h, nframes = it.table, it.lib, it.h, it.nframes
     pose_ptrs = it.pose_ptrs
     dev = torch.device("cuda", local_rank)
     stream = it.stream
-    occ = main_rec["occupied_blocks"]
+    occ = main_rec.get("occupied_blocks")          # (the mean over the resident frames: measured by --full only)
     sync = lambda: (table.synchronize(), torch.cuda.synchronize())        # noqa: E731
     extra = {}
 
@@ -830,7 +897,7 @@ def main():
 
     # ---- next rows ----
     # (the legs below hand float4 vertex maps to vh_preprocess / ICP / the oracle: a sensor-fed workload renders a few)
-    fposes, fverts = (poses, verts) if not it.sensor else render_frames(synth, wl, min(nframes, 24), dev, torch, sensor=False)
+    fposes, fverts = (poses, verts) if not (it.sensor and legs) else render_frames(synth, wl, min(nframes, 24), dev, torch, sensor=False)
     if "next" in legs:
         extra["next_rows"] = next_rows_leg(V, synth, torch, it, fverts, k_inv, stream, Wd, Ht)
     # ---- closed loop: track each frame against the model, integrate at the tracked pose, raycast ----
@@ -943,9 +1010,9 @@ def main():
         ms_per_step=main_rec["ms_per_step"], higher_is_better=True, scaling="weak",
         vs_baseline=None, dtype="f32", data="synthetic",
         metric_note="value = frames/s TSDF-integrated: a step is one vh_integrate_batch of frames_per_step consecutive "
-                    "resident frames (pipelined: one launch per frame), windows of exactly K steps with a synchronisation "
-                    "(which flushes the last frame) on both sides, median window; two_launch_frame = the same unpipelined; "
-                    "the raycast half of the metric is raycast_mpix_per_s",
+                    "resident frames (pipelined: one launch per frame), one window of exactly K steps with a synchronisation "
+                    "(which flushes the last frame) on both sides; two_launch_frame = the same unpipelined; "
+                    "the raycast half of the metric is raycast_mpix_per_s (--full)",
         frames_per_step=main_rec["frames_per_step"], ms_per_frame=main_rec["ms_per_frame"],
         windows=main_rec["windows"], timed_s=main_rec["timed_s"],
         window_min_ms=main_rec["window_min_ms"], window_max_ms=main_rec["window_max_ms"],
@@ -955,9 +1022,10 @@ def main():
         roofline=main_rec.get("roofline"), cpu_baseline=cpu,
         raycast_mpix_per_s=round(raycast_mpix, 1) if raycast_mpix else None,
         kernels=main_rec.get("kernels"),
-        frame_algorithmic_bytes=main_rec["frame_algorithmic_bytes"],
-        frame_algorithmic_gbs=main_rec["frame_algorithmic_gbs"],
-        frame_frac_of_hbm_peak=main_rec["frame_frac_of_hbm_peak"],
+        frame_algorithmic_bytes=main_rec.get("frame_algorithmic_bytes"),
+        frame_algorithmic_gbs=main_rec.get("frame_algorithmic_gbs"),
+        frame_frac_of_hbm_peak=main_rec.get("frame_frac_of_hbm_peak"),
+        full=args.full, outputs=main_rec.get("outputs"),
     )
     out.update(extra)
     if it is not None:

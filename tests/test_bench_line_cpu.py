@@ -61,3 +61,92 @@ def test_emit_prints_the_line_last_and_trims_if_it_must(tmp_path, monkeypatch):
     assert rec["value"] == full["value"] and rec["roofline"] and rec["cpu_baseline"]
     assert "trimmed" in err.getvalue() and "bench.py detail: {" in err.getvalue()
     assert json.load(open(tmp_path / "bench_detail.json"))["value"] == full["value"]
+
+
+def _args(monkeypatch, *argv):
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    return bench.parse_args()
+
+
+def test_plain_run_has_no_legs_and_full_has_them_all(monkeypatch, capsys):
+    a = _args(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert not a.full and a.leg_set == set() and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    assert _args(monkeypatch, "--full").leg_set == set(bench.ALL_LEGS)
+    assert _args(monkeypatch, "--full", "--legs", "cpu,raycast").leg_set == {"cpu", "raycast"}
+    assert _args(monkeypatch, "--full", "--no-cpu-baseline").leg_set == set(bench.ALL_LEGS) - {"cpu"}
+    assert _args(monkeypatch, "--legs", "none").leg_set == set()
+    for argv in (("--legs", "cpu"), ("--gpus", "2", "--dump-outputs", "d"), ("--sharded", "--dump-outputs", "d")):
+        try:
+            _args(monkeypatch, *argv)
+        except SystemExit as e:
+            assert e.code == 2
+        else:
+            raise AssertionError(argv)
+    assert "add --full" in capsys.readouterr().err
+
+
+class _FakeTable:
+    """The read-back surface dump_outputs uses, over a host model: n blocks in a shuffled hash table and heap."""
+
+    def __init__(self, n, visible):
+        import numpy as np
+        from voxelhashing_demo_amd import ENTRY_DTYPE, VOXEL_DTYPE
+        rng = np.random.default_rng(1)
+        pos = rng.choice(64 ** 3, n, replace=False)
+        self.pos = np.stack([pos // 4096 - 32, pos // 64 % 64 - 32, pos % 64 - 32], 1).astype(np.int32)
+        self.ht = np.zeros(3 * n, ENTRY_DTYPE)
+        self.ht["ptr"] = -1
+        slots, heap = rng.permutation(3 * n)[:n], rng.permutation(n)
+        self.ht["pos"][slots], self.ht["ptr"][slots] = self.pos, 512 * heap
+        self.vol = np.zeros(512 * n, VOXEL_DTYPE)
+        for p, h in zip(self.pos, heap):          # a block's voxels are a function of its position only
+            self.vol["sdf"][512 * h:512 * h + 512] = p.sum() + np.arange(512) / 512.0
+            self.vol["weight"][512 * h:512 * h + 512] = 1 + abs(p[0])
+        self.visible = self.ht[slots[:visible]]
+
+    def synchronize(self):
+        pass
+
+    def hash_table(self):
+        return self.ht.copy()
+
+    def compact(self):
+        return self.visible.copy()
+
+    def block_voxels(self, ptr):
+        return self.vol[ptr:ptr + 512].copy()
+
+
+def _load(d):
+    import numpy as np
+    return {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+
+
+def test_dump_outputs_sorted_and_complete(tmp_path):
+    import numpy as np
+    t = _FakeTable(300, 40)
+    shapes = bench.dump_outputs(str(tmp_path), t)
+    out = _load(tmp_path)
+    assert shapes == {k: list(v.shape) for k, v in out.items()}
+    assert set(out) == {"blocks_pos", "visible_pos", "voxels_pos", "voxels_sdf", "voxels_weight"}
+    assert all(v.dtype == np.float32 for v in out.values())
+    want = t.pos[np.lexsort((t.pos[:, 2], t.pos[:, 1], t.pos[:, 0]))].astype(np.float32)
+    assert np.array_equal(out["blocks_pos"], want) and np.array_equal(out["voxels_pos"], want)
+    assert len(out["visible_pos"]) == 40
+    assert np.array_equal(out["voxels_sdf"][:, 0], want.sum(1)) and np.array_equal(out["voxels_weight"][:, 7], 1 + abs(want[:, 0]))
+
+
+def test_dump_outputs_samples_beyond_its_caps_with_a_fixed_seed(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_VOXEL_BLOCKS", 50)
+    monkeypatch.setattr(bench, "DUMP_POS_ROWS", 120)
+    t = _FakeTable(300, 200)
+    bench.dump_outputs(str(tmp_path / "a"), t)
+    bench.dump_outputs(str(tmp_path / "b"), _FakeTable(300, 200))
+    a, b = _load(tmp_path / "a"), _load(tmp_path / "b")
+    assert len(a["voxels_pos"]) == 50 and len(a["blocks_pos"]) == 120 and len(a["visible_pos"]) == 120
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert set(map(tuple, a["voxels_pos"])) <= set(map(tuple, t.pos.astype(np.float32)))
+    assert np.array_equal(a["voxels_sdf"][:, 0], a["voxels_pos"].sum(1))
+    assert (np.diff(a["voxels_pos"][:, 0]) >= 0).all()

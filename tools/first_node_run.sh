@@ -51,7 +51,7 @@ p = (r.get('predicted') or {}).get('reference_walk', {}).get('frames_per_s')
 print('   n_gpus', r['n_gpus'], 'value', r['value'], 'frames/s; predicted (nominal)', p, '; phases', r.get('exchange_phases_us'), '; form', r.get('generation_form'),
       '; ranks', (r.get('exchange_ranks') or {}).get('ranks'), 'self-check', (r.get('exchange_ranks') or {}).get('self_check'), '; bin overflows', r['config'].get('key_bin_overflows'))"; }
 echo "== N = 1: bench.py (leg sharded_world1) and bench.py --sharded"
-timeout 1200 python3 bench.py --workload $WL > $OUT/n1_default.out 2> $OUT/n1_default.err
+timeout 1200 python3 bench.py --full --workload $WL > $OUT/n1_default.out 2> $OUT/n1_default.err
 tail -n 1 $OUT/n1_default.out | python3 -c "
 import sys, json
 r = json.loads(sys.stdin.read()); print('   value', r['value'], 'sharded_world1', r['legs'].get('sharded_world1'))"

@@ -6,6 +6,6 @@ OUT=gpurun_out/r04; mkdir -p $OUT
 (for MB in 419 1680; do echo "== $MB MB"; /tmp/membw $MB | grep -E "ptr|dwordx4 nt"; done) > $OUT/membw_shapes.txt 2>&1
 for o in walk_entries=4 walk_entries=8; do for w in C3 C5table; do
   echo "$w $o"
-  python3 bench.py --workload $w --legs none --option $o 2>/dev/null | python3 -c "import sys,json; r=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print(r['value'], r['roofline']['us_per_launch'], r['roofline']['frac'])"
+  python3 bench.py --full --workload $w --legs none --option $o 2>/dev/null | python3 -c "import sys,json; r=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print(r['value'], r['roofline']['us_per_launch'], r['roofline']['frac'])"
 done; done > $OUT/walk_entries_ab.txt 2>&1
 cat $OUT/membw_shapes.txt $OUT/walk_entries_ab.txt

@@ -6,10 +6,10 @@ q() { python3 -c "import sys,json; r=json.loads([l for l in sys.stdin if l.start
 for WL in C3 C5table; do
   for SP in 0 50 70 85 100; do
     echo -n "$WL claim_span=$SP: " | tee -a $OUT/span.txt
-    python3 bench.py --workload $WL --legs none --steps 100 --warmup 20 --option claim_span=$SP 2>/dev/null | q | tee -a $OUT/span.txt
+    python3 bench.py --full --workload $WL --legs none --steps 100 --warmup 20 --option claim_span=$SP 2>/dev/null | q | tee -a $OUT/span.txt
   done
   for SK in 0 4 8; do
     echo -n "$WL debug_skip_roles=$SK (4: no claim tiles, 8: no walk): " | tee -a $OUT/span.txt
-    VOXELHASH_LIB=voxelhashing_demo_amd/lib/alt/v_skip.so python3 bench.py --workload $WL --legs none --steps 100 --warmup 20 --option debug_skip_roles=$SK 2>/dev/null | q | tee -a $OUT/span.txt
+    VOXELHASH_LIB=voxelhashing_demo_amd/lib/alt/v_skip.so python3 bench.py --full --workload $WL --legs none --steps 100 --warmup 20 --option debug_skip_roles=$SK 2>/dev/null | q | tee -a $OUT/span.txt
   done
 done

@@ -5,6 +5,6 @@ q() { python3 -c "
 import json,sys; p=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print('value', p['value'], 'us/launch', p['roofline'].get('us_per_launch'))"; }
 for i in 1 2 3; do
 for args in "--workload C3 --option flatten_variant=4" "--workload C5table --option flatten_variant=4"; do
-  echo -n "$args test first in the drain: " | tee -a $OUT/drain.txt; VOXELHASH_LIB=voxelhashing_demo_amd/lib/alt/v_nodrain.so python3 bench.py --legs none --no-cpu-baseline $args 2>/dev/null | q | tee -a $OUT/drain.txt
-  echo -n "$args slot first in the drain: " | tee -a $OUT/drain.txt; python3 bench.py --legs none --no-cpu-baseline $args 2>/dev/null | q | tee -a $OUT/drain.txt
+  echo -n "$args test first in the drain: " | tee -a $OUT/drain.txt; VOXELHASH_LIB=voxelhashing_demo_amd/lib/alt/v_nodrain.so python3 bench.py --full --legs none --no-cpu-baseline $args 2>/dev/null | q | tee -a $OUT/drain.txt
+  echo -n "$args slot first in the drain: " | tee -a $OUT/drain.txt; python3 bench.py --full --legs none --no-cpu-baseline $args 2>/dev/null | q | tee -a $OUT/drain.txt
 done; done

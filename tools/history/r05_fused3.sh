@@ -8,4 +8,4 @@ for i in 1 2; do
 for v in gen8 gen12 gen16; do echo -n "fused $v: " | tee -a $OUT/ab3.txt; VOXELHASH_LIB=voxelhashing_demo_amd/lib/alt/v_$v.so python3 bench.py --sharded --legs none 2>/dev/null | q | tee -a $OUT/ab3.txt; done
 echo -n "separate: " | tee -a $OUT/ab3.txt; python3 bench.py --sharded --legs none --option fused_generation=0 2>/dev/null | q | tee -a $OUT/ab3.txt
 done
-echo -n "unsharded + fused groups=4: " | tee -a $OUT/ab3.txt; python3 bench.py --legs sharded 2>/dev/null | q | tee -a $OUT/ab3.txt
+echo -n "unsharded + fused groups=4: " | tee -a $OUT/ab3.txt; python3 bench.py --full --legs sharded 2>/dev/null | q | tee -a $OUT/ab3.txt

@@ -8,4 +8,4 @@ for i in 1 2; do
 for v in prio3 prio1; do echo -n "fused groups 8, $v: " | tee -a $OUT/ab4.txt; VOXELHASH_LIB=voxelhashing_demo_amd/lib/alt/v_$v.so python3 bench.py --sharded --legs none 2>/dev/null | q | tee -a $OUT/ab4.txt; done
 echo -n "fused groups 8: " | tee -a $OUT/ab4.txt; python3 bench.py --sharded --legs none 2>/dev/null | q | tee -a $OUT/ab4.txt
 done
-echo -n "unsharded + fused groups 8: " | tee -a $OUT/ab4.txt; python3 bench.py --legs sharded 2>/dev/null | q | tee -a $OUT/ab4.txt
+echo -n "unsharded + fused groups 8: " | tee -a $OUT/ab4.txt; python3 bench.py --full --legs sharded 2>/dev/null | q | tee -a $OUT/ab4.txt

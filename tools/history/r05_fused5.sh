@@ -9,4 +9,4 @@ for i in 1 2; do
 for v in nopf8 pf12 pf16 pf24 pf16rc; do echo -n "$v: " | tee -a $OUT/ab5.txt; VOXELHASH_LIB=voxelhashing_demo_amd/lib/alt/v_$v.so python3 bench.py --sharded --legs none 2>/dev/null | q | tee -a $OUT/ab5.txt; done
 echo -n "prefetch, groups 8: " | tee -a $OUT/ab5.txt; python3 bench.py --sharded --legs none 2>/dev/null | q | tee -a $OUT/ab5.txt
 done
-echo -n "unsharded + prefetch groups 8: " | tee -a $OUT/ab5.txt; python3 bench.py --legs sharded 2>/dev/null | q | tee -a $OUT/ab5.txt
+echo -n "unsharded + prefetch groups 8: " | tee -a $OUT/ab5.txt; python3 bench.py --full --legs sharded 2>/dev/null | q | tee -a $OUT/ab5.txt

@@ -8,4 +8,4 @@ for i in 1 2 3; do
 for v in before; do echo -n "$v: " | tee -a $OUT/ab8.txt; VOXELHASH_LIB=voxelhashing_demo_amd/lib/alt/v_$v.so python3 bench.py --sharded --legs none 2>/dev/null | q | tee -a $OUT/ab8.txt; done
 echo -n "in-tree (6 groups, tiles stepped): " | tee -a $OUT/ab8.txt; python3 bench.py --sharded --legs none 2>/dev/null | q | tee -a $OUT/ab8.txt
 done
-echo -n "unsharded + in-tree: " | tee -a $OUT/ab8.txt; python3 bench.py --legs sharded 2>/dev/null | q | tee -a $OUT/ab8.txt
+echo -n "unsharded + in-tree: " | tee -a $OUT/ab8.txt; python3 bench.py --full --legs sharded 2>/dev/null | q | tee -a $OUT/ab8.txt

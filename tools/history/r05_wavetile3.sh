@@ -7,8 +7,8 @@ timeout 1500 python -m pytest tests/test_gpu_pipeline.py tests/test_gpu_bench_pa
 for i in 1 2; do
 for wl in C2 C3 C5table; do
   for o in 0 2; do
-  echo -n "$wl flatten_variant=4 claim_wave_tiles=$o: " | tee -a $OUT/auto.txt; python3 bench.py --legs none --no-cpu-baseline --workload $wl --option flatten_variant=4 --option claim_wave_tiles=$o 2>/dev/null | q | tee -a $OUT/auto.txt
+  echo -n "$wl flatten_variant=4 claim_wave_tiles=$o: " | tee -a $OUT/auto.txt; python3 bench.py --full --legs none --no-cpu-baseline --workload $wl --option flatten_variant=4 --option claim_wave_tiles=$o 2>/dev/null | q | tee -a $OUT/auto.txt
   done
 done
-echo -n "C2 reference walk: " | tee -a $OUT/auto.txt; python3 bench.py --legs none --no-cpu-baseline --workload C2 2>/dev/null | q | tee -a $OUT/auto.txt
+echo -n "C2 reference walk: " | tee -a $OUT/auto.txt; python3 bench.py --full --legs none --no-cpu-baseline --workload C2 2>/dev/null | q | tee -a $OUT/auto.txt
 done

@@ -25,7 +25,7 @@ out = json.load(open(out_path)) if os.path.exists(out_path) else {}
 for wl in sys.argv[2:]:
     f = json.load(open(os.path.join(src, f"pmc_FETCH_SIZE_{wl}.json")))
     w = json.load(open(os.path.join(src, f"pmc_WRITE_SIZE_{wl}.json")))
-    d = {"source": f"{src}: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, bench.py --legs none --workload "
+    d = {"source": f"{src}: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, bench.py --full --legs none --workload "
                    f"{wl} --steps 100 --warmup 10, mean over dispatches after the first 10",
          "correction": "hbm_bytes = 2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950: FETCH_SIZE counts 128-B requests as 64 B)"}
     for k in sorted(set(f) | set(w)):
@@ -53,7 +53,7 @@ for wl in sys.argv[2:]:
         for k, cs in sorted(v.items(), key=lambda kv: 0 if kv[0].startswith("raycast_coop_kernel<false>") else 1 if kv[0].startswith(("raycast_coop", "raycast_dda")) else 2):
             if k.startswith(("raycast_coop_kernel", "raycast_dda_kernel", "raycast_kernel")) and "SQ_INSTS_VALU" in cs and "SQ_WAVES" in cs:
                 out[wl + "_raycast"] = {
-                    "source": f"{src}: rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES, bench.py --legs raycast --workload {wl}",
+                    "source": f"{src}: rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES, bench.py --full --legs raycast --workload {wl}",
                     "kernel": k.split("(")[0],
                     "raycast_kernel_valu_insts": cs["SQ_INSTS_VALU"]["mean"], "raycast_kernel_waves": cs["SQ_WAVES"]["mean"],
                     "raycast_kernel_valu_per_wave": round(cs["SQ_INSTS_VALU"]["mean"] / max(1.0, cs["SQ_WAVES"]["mean"]), 1)}
@@ -69,7 +69,7 @@ for wl in sys.argv[2:]:
     if not os.path.exists(f):
         continue
     rows = [r for r in csv.DictReader(l for l in open(f) if not l.startswith("#"))]
-    d = {"source": f"{f}: rocprofv3 --kernel-trace --stats of bench.py --legs none --workload {wl}"}
+    d = {"source": f"{f}: rocprofv3 --kernel-trace --stats of bench.py --full --legs none --workload {wl}"}
     for r in rows:
         name = r["Name"]
         i = name.find("vh::")

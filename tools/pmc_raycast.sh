@@ -13,7 +13,7 @@ for G in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_SMEM" \
          "TA_BUSY_avr TA_TA_BUSY_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" \
          "TCP_GATE_EN1_sum TCP_GATE_EN2_sum TCP_TA_TCP_STATE_READ_sum TCP_PENDING_STALL_CYCLES_sum"; do
   i=$((i+1))
-  rocprofv3 --pmc $G --output-format csv -d $T/g$i -- python3 bench.py --legs raycast --workload C2 --steps 20 --warmup 5 --profile-steps 0 > $OUT/g$i.log 2>&1
+  rocprofv3 --pmc $G --output-format csv -d $T/g$i -- python3 bench.py --full --legs raycast --workload C2 --steps 20 --warmup 5 --profile-steps 0 > $OUT/g$i.log 2>&1
   python3 tools/prof_summary.py pmc $T/g$i $OUT/pmc_g$i.json 2 > /dev/null 2>&1
   python3 - <<PY
 import json

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 {
 for env in "X=1" "VH_ICP_PERSISTENT=0" "VH_ICP_BLOCKS=240" "VH_ICP_BLOCKS=200" "VH_ICP_BLOCKS=160" "VH_ICP_BLOCKS=128" "VH_ICP_BLOCKS=255"; do
   echo "== $env"
-  env $env timeout 300 python bench.py --legs loop --steps 5 --warmup 2 > /dev/null 2>&1
+  env $env timeout 300 python bench.py --full --legs loop --steps 5 --warmup 2 > /dev/null 2>&1
   python - <<'PY'
 import json
 d=json.load(open("bench_detail.json"))["closed_loop"]

@@ -9,11 +9,11 @@ LIBV=voxelhashing_demo_amd/lib/alt/v_skip.so
 WL=${1:-C2}
 echo "# $WL walk-free frame, roles switched off (diagnostics build): launch us (HIP events) and counter bytes per launch" | tee $OUT/index_roles_$WL.txt
 for SK in 0 2 4 8 6 10 12 14; do
-  VOXELHASH_LIB=$LIBV timeout 300 python3 bench.py --legs none --workload $WL --option flatten_variant=4 --option debug_skip_roles=$SK > /tmp/b.out 2>/dev/null
+  VOXELHASH_LIB=$LIBV timeout 300 python3 bench.py --full --legs none --workload $WL --option flatten_variant=4 --option debug_skip_roles=$SK > /tmp/b.out 2>/dev/null
   US=$(python3 -c "import json;print(json.load(open('bench_detail.json'))['roofline']['us_per_launch'])")
   for C in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_$C
-    VOXELHASH_LIB=$LIBV rocprofv3 --pmc $C --output-format csv -d /tmp/pmc_$C -- python3 bench.py --legs none --workload $WL --option flatten_variant=4 --option debug_skip_roles=$SK --steps 100 --warmup 10 --profile-steps 0 > /dev/null 2>&1
+    VOXELHASH_LIB=$LIBV rocprofv3 --pmc $C --output-format csv -d /tmp/pmc_$C -- python3 bench.py --full --legs none --workload $WL --option flatten_variant=4 --option debug_skip_roles=$SK --steps 100 --warmup 10 --profile-steps 0 > /dev/null 2>&1
     python3 tools/prof_summary.py pmc /tmp/pmc_$C /tmp/pmc_$C.json 10 > /dev/null
   done
   python3 - <<PY | tee -a $OUT/index_roles_$WL.txt

@@ -7,7 +7,7 @@ OUT=gpurun_out/r06; mkdir -p $OUT
 for WL in C2 C2index; do
   EX=""; [ "$WL" = "C2index" ] && EX="--option flatten_variant=4"
   rm -rf /tmp/pmc_rd
-  rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d /tmp/pmc_rd -- python3 bench.py --legs none --workload C2 $EX --steps 100 --warmup 10 --profile-steps 0 > /dev/null 2>&1
+  rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d /tmp/pmc_rd -- python3 bench.py --full --legs none --workload C2 $EX --steps 100 --warmup 10 --profile-steps 0 > /dev/null 2>&1
   python3 tools/prof_summary.py pmc /tmp/pmc_rd $OUT/pmc_RDREQ_32B_$WL.json 10 > /dev/null 2>&1
   python3 - <<PY
 import json
