@@ -338,7 +338,7 @@ int vh_download_range(vh_context *ctx, int which, size_t offset_bytes, void *hos
 
 /* DIAGNOSTICS AND TEST FACILITIES.  They are part of the library a deployment loads -- the tests and the profiles run on the
  * product, not on a build of their own -- and are supported as documented here; none of them changes a result:
- *   vh_debug_eval, vh_debug_set_raycast_stamps, vh_debug_occupy (below); the loop-back transport of voxelhash_dist.h
+ *   vh_debug_eval, vh_debug_set_raycast_stamps, vh_debug_occupy, vh_debug_icp_layout (below); the loop-back transport of voxelhash_dist.h
  *   (vh_dist_loopback_id: the N-rank exchange inside one process); vh_set_profiling / vh_get_kernel_times; the options
  *   "spin_limit"; environment: VOXELHASH_ROCTX=1 (roctx ranges named after the entry points -- vh_integrate, vh_integrate_depth,
  *   vh_flush, vh_raycast, vh_render_blocks, vh_icp_align, vh_garbage_collect, vh_preprocess, vh_dist_step_batch, vh_dist_raycast --
@@ -355,6 +355,11 @@ int vh_debug_eval(vh_context *ctx, const vh_float4 *d_points, int32_t n, int32_t
 int vh_debug_set_raycast_stamps(vh_context *ctx, void *d_stamps);
 /* test hook: `workgroups` x 256 lanes that stay resident for `microseconds` on `stream` (a device busy with another kernel) */
 int vh_debug_occupy(vh_context *ctx, void *stream, int32_t workgroups, int32_t microseconds);
+/* test hook: the grids vh_icp_create chose -- out[0] workgroups of an ICP round (VH_ICP_BLOCKS), out[1] workgroups of the
+ * one-launch Align, out[2] its input pixels per lane held in registers (1..6; 0: read again every round; -1: Align runs as a
+ * chain of one-launch rounds, VH_ICP_PERSISTENT=0 or a grid the chip cannot hold at once) */
+struct vh_icp;
+int vh_debug_icp_layout(const struct vh_icp *icp, int32_t out[3]);
 
 /* Options (18 names; anything else is rejected with VH_ERR_INVALID_ARGUMENT).  Results never depend on the tuning ones.
  *   semantics of the model (extensions of the reference, each with its oracle counterpart):
@@ -618,8 +623,8 @@ int vh_icp_correspondences(vh_icp *icp, const vh_float4 *d_input, const vh_float
 int  vh_icp_solve(const vh_icp_system *sys, double estimate[6]);
 void vh_se3_exp(const double twist[6], double T[16]);
 void vh_se3_log(const double T[16], double twist[6]);
-/* Up to max_iters rounds (the reference: 20) from the start value in `delta`, which receives the
- * result; stops early when the summed residual is exactly 0 (:52) or the system is singular.
+/* Up to max_iters rounds (the reference: 20; 0 <= max_iters <= 65536, else VH_ERR_INVALID_ARGUMENT) from the start value
+ * in `delta`, which receives the result; stops early when the summed residual is exactly 0 (:52) or the system is singular.
  * All rounds run in ONE launch whose workgroups wait for each other between rounds
  * (VH_ICP_PERSISTENT=0 in the environment at vh_icp_create: one launch per round -- same result,
  * bit for bit).  The waits are bounded: VH_ERR_TIMEOUT when a

@@ -37,6 +37,23 @@ def maps_on_both(oracle, torch, depth, kinv):
     return po, no, pg, ng
 
 
+def expected_layout(w, h, blocks=None):
+    """vh_icp_create's rule: (round grid, one-launch grid, pixels per lane in registers -- 0: read again every round)."""
+    npix = w * h
+    most = -(-npix // 256)
+    g = min(most, 512 if npix > 6 * 256 * 256 else 256) if blocks is None else max(1, min(most, blocks))
+    slots = -(-npix // (g * 256))
+    return (g, g, slots if slots <= 6 else 0)
+
+
+def icp_layout(trk):
+    """(round grid, one-launch grid, pixels per lane; -1: the chain of rounds) of a CameraTracking (vh_debug_icp_layout)."""
+    from voxelhashing_demo_amd import _lib as L
+    out = (C.c_int32 * 3)()
+    L.check(L.load().vh_debug_icp_layout(trk._h, out), "vh_debug_icp_layout")
+    return tuple(out)
+
+
 def close_sums(got, want):
     JTJ, JTr, err, cnt = got
     oJTJ, oJTr, oerr, ocnt = want
@@ -289,8 +306,9 @@ def test_raycast_maps_is_raycast_plus_depth_to_maps(oracle, vh, torch_cuda):
     assert (on[..., :3] != 0).any(axis=-1).sum() > 10000
 
 
-# (pixels per lane of the one-launch kernel: 1, 2, 3, 4, 5, 6 in registers -- one instantiation each -- and 7 / 19: the
-# instantiation that reads the points again every round)
+# (pixels per lane of the one-launch kernel: 1 on 192 workgroups, 2, 3, 4, 5, 6 in registers on 256 -- one instantiation each
+# -- then 4 on 512 (800x560), and at 1280x960 the instantiation that reads the points again every round, on 512; the layout is
+# asserted, so that the one-launch side is not the chain's fall-back.  Other sizes and grids: tests/test_gpu_icp_edges.py)
 @pytest.mark.parametrize("size", [(256, 192), (320, 240), (480, 360), (512, 480), (640, 480), (800, 480), (800, 560), (1280, 960)])
 def test_one_launch_align_equals_the_chain_of_rounds(vh, torch_cuda, size, monkeypatch):
     """vh_icp_align runs all rounds in ONE launch (icp_align_kernel: input points in registers, the estimate handed from
@@ -318,6 +336,7 @@ def test_one_launch_align_equals_the_chain_of_rounds(vh, torch_cuda, size, monke
         for flags in (0, 3):
             for iters in (20, 7, 1):
                 trk = tracking.CameraTracking(w, h, K, flags=flags, max_iters=iters)
+                assert icp_layout(trk) == (expected_layout(w, h) if form == "one_launch" else expected_layout(w, h)[:2] + (-1,))
                 d = trk.Align(v[101], *maps[100]).copy()                          # a real step of the camera
                 out.append((d, trk.last, trk.iterations))
                 d = trk.Align(v[101], maps[100][0], nothing).copy()               # a target without normals: residual 0, stop

@@ -104,6 +104,7 @@ SIGNATURES = {
     "vh_raycast_normals": (C.c_int, [_vp, _fp, _f, _f, _vp, _vp]),
     "vh_debug_set_raycast_stamps": (C.c_int, [_vp, _vp]),
     "vh_debug_occupy": (C.c_int, [_vp, _vp, _i32, _i32]),
+    "vh_debug_icp_layout": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "vh_render_blocks": (C.c_int, [_vp, _fp, _f, _f, _vp, _vp]),
     "vh_icp_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "vh_icp_destroy": (C.c_int, [_vp]),

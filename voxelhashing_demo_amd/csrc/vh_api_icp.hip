@@ -21,6 +21,7 @@ struct vh_icp {
 };
 
 constexpr int kIcpAlignMaxSlots = 6;
+constexpr int kIcpMaxIters = 1 << 16;     // vh_icp_align's bound on max_iters (include/voxelhash.h)
 
 static const void *icp_align_entry(int slots)
 {
@@ -92,6 +93,17 @@ extern "C" int vh_icp_create(int32_t width, int32_t height, int32_t device, vh_i
         return fail(e == hipErrorOutOfMemory ? VH_ERR_OUT_OF_MEMORY : VH_ERR_HIP, "icp workspace", e);
     }
     *out = p;
+    return VH_OK;
+}
+
+// The layout vh_icp_create chose (tests): the round grid, the one-launch grid, and its pixels per lane in registers (0: the
+// points are read again every round; -1: Align is the chain of one-launch rounds).
+extern "C" int vh_debug_icp_layout(const vh_icp *p, int32_t out[3])
+{
+    if (!p || !out) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
+    out[0] = p->blocks;
+    out[1] = p->alignBlocks;
+    out[2] = p->alignSlots;
     return VH_OK;
 }
 
@@ -205,6 +217,10 @@ extern "C" int vh_icp_align(vh_icp *p, const vh_float4 *d_input, const vh_float4
     VH_TRACE("vh_icp_align");
     if (!p || !d_input || !d_target || !d_target_normals || !K || !delta || max_iters < 0)
         return fail(VH_ERR_INVALID_ARGUMENT, "bad argument");
+    // A bound on the rounds: the one-launch Align hands out max_iters sequence numbers per call from seqBase, which is reset
+    // once it passes 2^30 (below), so the numbers stay below 2^30 + 2^16 < 2^31 -- they are ints in the kernel, and the
+    // stop is published as the negated number
+    if (max_iters > kIcpMaxIters) return fail(VH_ERR_INVALID_ARGUMENT, "vh_icp_align: max_iters above 65536");
     DeviceGuard guard(p->device);
     const auto hostT0 = std::chrono::steady_clock::now();
     IcpState &hs = *p->hostState;
@@ -273,7 +289,7 @@ extern "C" int vh_icp_align(vh_icp *p, const vh_float4 *d_input, const vh_float4
         static unsigned long long st[512 + 1024];
         VH_HIP(hipMemcpy(st, p->stamps, sizeof st, hipMemcpyDeviceToHost));
         std::fprintf(stderr, "icp stamps round 10, record stored (us after workgroup 0 started the round), by workgroup:");
-        for (int b = 0; b < p->alignBlocks; ++b) std::fprintf(stderr, "%s%5.2f", b % 16 ? " " : "\n  ", ((double)st[512 + b] - (double)st[80]) * 0.01);
+        for (int b = 0; b < std::min(p->alignBlocks, 1024); ++b) std::fprintf(stderr, "%s%5.2f", b % 16 ? " " : "\n  ", ((double)st[512 + b] - (double)st[80]) * 0.01);
         std::fprintf(stderr, "\n");
     }
     if (hs.timeout) return fail(VH_ERR_TIMEOUT, "vh_icp_align: a workgroup of the one-launch Align gave up waiting for a round's estimate");

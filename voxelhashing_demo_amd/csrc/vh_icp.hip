@@ -509,8 +509,10 @@ __global__ __launch_bounds__(kIcpThreads) void icp_align_kernel(IcpParams ip, co
                                                                 unsigned long long *__restrict__ stamps)
 {
     // diagnostics (VH_ICP_STAMPS=1): s_memrealtime (100 MHz) per round, workgroup 0: [0] round starts, [1] sums in registers,
-    // [2] record stored, [3] all records seen, [4] added, [5] next estimate published; the last workgroup: [6] round starts, [7] record stored
-#define VH_ICP_STAMP(i) do { if (stamps && blockIdx.x == 0 && threadIdx.x == 0) stamps[(size_t)round * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+    // [2] record stored, [3] all records seen, [4] added, [5] next estimate published; the last workgroup: [6] round starts, [7] record stored.
+    // Rounds 0..63 only (words 0..511, what vh_icp_align reads back), and at round 10 word 512 + b of workgroup b < 1024: the
+    // allocation is 512 + 1024 words whatever max_iters and the grid are
+#define VH_ICP_STAMP(i) do { if (stamps && round < 64 && blockIdx.x == 0 && threadIdx.x == 0) stamps[(size_t)round * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
     __shared__ float4 sums4[kIcpSumFloats / 4];
     __shared__ float sm[8][kIcpStride];
     __shared__ float total[kIcpStride];
@@ -537,7 +539,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_align_kernel(IcpParams ip, co
 #pragma unroll
         for (int i = 0; i < 12; ++i) ip.delta[i] = sDelta[i];
         VH_ICP_STAMP(0);
-        if (stamps && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) stamps[(size_t)round * 8 + 6] = __builtin_amdgcn_s_memrealtime();
+        if (stamps && round < 64 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) stamps[(size_t)round * 8 + 6] = __builtin_amdgcn_s_memrealtime();
         float acc[kIcpTerms];
 #pragma unroll
         for (int k = 0; k < kIcpTerms; ++k) acc[k] = 0.0f;
@@ -593,8 +595,8 @@ __global__ __launch_bounds__(kIcpThreads) void icp_align_kernel(IcpParams ip, co
                 icp_store_word(&records[(size_t)blockIdx.x * kIcpStride + (threadIdx.x >> 3)], icp_word(v, want));
         }
         VH_ICP_STAMP(2);
-        if (stamps && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) stamps[(size_t)round * 8 + 7] = __builtin_amdgcn_s_memrealtime();
-        if (stamps && round == 10 && threadIdx.x == 0) stamps[512 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+        if (stamps && round < 64 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) stamps[(size_t)round * 8 + 7] = __builtin_amdgcn_s_memrealtime();
+        if (stamps && round == 10 && blockIdx.x < 1024 && threadIdx.x == 0) stamps[512 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
         if (blockIdx.x != 0) {
             if (finalRound) return;
             // wait for the estimate of the next round (or the stop): the copy of this workgroup's octet
@@ -639,11 +641,15 @@ __global__ __launch_bounds__(kIcpThreads) void icp_align_kernel(IcpParams ip, co
 #define VH_ICP_NAP 16
 #endif
         __builtin_amdgcn_s_sleep(VH_ICP_NAP);
-        for (int b0 = part; b0 < numBlocks; b0 += 8 * 32) {
+        // every wave makes the same number of passes (the loop body has a barrier): a part whose records all lie beyond the
+        // grid (fewer than 8 workgroups, or numBlocks % 256 in 1..7) rides along with nothing missing and adds +0.0f, as in
+        // icp_sum_records -- the order of additions is unchanged
+        for (int base = 0; base < numBlocks; base += 8 * 32) {
             // a word that has been seen is kept (in registers: parked in LDS the round took 9.0 instead of 8.3 us); every pass
             // asks again only for the halves of 16 words somebody in the wave still misses one of (quarters of eight: four
             // round trips in a row for a full pass, slower), so the pass that finds the slowest workgroup's record is a
             // round trip of 16 loads, not of all 32
+            const int b0 = base + part;
             uint32_t missing = 0xffffffffu;
             float r[32];
 #pragma unroll
@@ -658,7 +664,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_align_kernel(IcpParams ip, co
 #pragma unroll
                     for (int u = 0; u < 16; ++u) {
                         const int b = b0 + 8 * (16 * h + u);
-                        w[u] = icp_load_word(&records[(size_t)(b < numBlocks ? b : b0) * kIcpStride + kk]);
+                        w[u] = icp_load_word(&records[(size_t)(b < numBlocks ? b : base) * kIcpStride + kk]);   // (base: in the grid, b0 may not be)
                     }
 #pragma unroll
                     for (int u = 0; u < 16; ++u) {
