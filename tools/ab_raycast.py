@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of a raycast / silhouette option in ONE process, interleaved rounds (per-dispatch HIP event timing).
 
-  python tools/ab_raycast.py --option raycast_patch --values 0 1 [--workload C2]
+  python tools/ab_raycast.py --option raycast_beam --values 0 1 [--workload C2]
 """
 import argparse
 import os
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", default="raycast_patch")
+    ap.add_argument("--option", default="raycast_beam")
     ap.add_argument("--values", type=int, nargs="+", default=[0, 1])
     ap.add_argument("--workload", default="C2")
     ap.add_argument("--frames", type=int, default=120)

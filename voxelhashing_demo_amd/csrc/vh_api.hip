@@ -101,10 +101,52 @@ struct MultiPending {
     int packetFormat = 0;
 };
 
+// Move-only owner of one device allocation.  Everything else that names device memory (DevPtrs, claimBuf[] ...) is a
+// view into one of these.  The destructor frees on the CURRENT device: owners are released under their object's DeviceGuard.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;                  // elements it was allocated for
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(n, o.n); o.reset(); return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    // a fresh allocation of `count` elements; empty on failure.  try_alloc: for optional buffers (no error text, nothing else touched)
+    hipError_t try_alloc(size_t count)
+    {
+        reset();
+        const hipError_t e = hipMalloc((void **)&p, sizeof(T) * count);
+        if (e == hipSuccess) n = count; else p = nullptr;
+        return e;
+    }
+    int alloc(size_t count, const char *what)
+    {
+        const hipError_t e = try_alloc(count);
+        if (e == hipSuccess) return VH_OK;
+        return fail(e == hipErrorOutOfMemory ? VH_ERR_OUT_OF_MEMORY : VH_ERR_HIP, (std::string("hipMalloc ") + what).c_str(), e);
+    }
+    // grow on demand: the caller has synchronised whatever still uses the old allocation
+    int reserve(size_t count, const char *what) { return n >= count && p ? VH_OK : alloc(count, what); }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    size_t size() const { return n; }
+};
+
 struct vh_context {
     HashTableParams params;
     FrameParams fp;
-    DevPtrs dp;
+    // What the context OWNS.  dp, claimBuf[], candBuf[], compactBuf[], compactHome below are views into these: they alias and
+    // swap freely (pipe_view, settle) and never decide what is freed.  [1] of a pair: the pipelined frames' second set.
+    DevBuf<uint32_t> heap, candTarget, gcMarks, compactMask, bucketBits, macroBits;
+    DevBuf<VoxelEntry> table, compact[2];
+    DevBuf<unsigned long long> claim[2];
+    DevBuf<Voxel> blocks;
+    DevBuf<int32_t> counters;
+    DevBuf<int4> candidates[2];
+    DevPtrs dp;                    // the kernels' view of them (vh_device.h)
     int device = 0;
     hipStream_t stream = nullptr;
     size_t numEntries = 0;         // owned entries
@@ -133,7 +175,7 @@ struct vh_context {
     uint32_t allocEpoch = 0;       // lock epoch (epochTotal) of the last allocBlocks (overflow list: one per epoch)
     uint32_t epochTotal = 0;       // lock epochs since creation (fp.epoch is the 9-bit epoch of the claim words)
     // pipelined frames (option "pipeline", vh_integrate_batch; vh_frame.hip)
-    float *fusedPlane = nullptr;   // packed camera-z plane launch 1 of the two-launch frame leaves for launch 2 (large images)
+    DevBuf<float> fusedPlane;      // packed camera-z plane launch 1 of the two-launch frame leaves for launch 2 (large images)
     int pipeline = 0;
     int pipeIntegrateGrid = 512;   // workgroups of the deferred TSDF update inside a pipelined launch
     bool pipePending = false;      // the commit + TSDF update of the last frame are still to be launched
@@ -146,8 +188,8 @@ struct vh_context {
     unsigned long long *claimBuf[2] = {nullptr, nullptr};
     int4 *candBuf[2] = {nullptr, nullptr};
     VoxelEntry *compactBuf[2] = {nullptr, nullptr};
-    uint32_t *claimFilter = nullptr;       // pipelined frames: three claim filters of kPendFilterWords words (vh_alloc.hip: pend_maybe)
-    uint32_t *maskBuf2 = nullptr;          // pipelined multi-camera frames: the camera masks of the second compact buffer
+    DevBuf<uint32_t> claimFilter;          // pipelined frames: three claim filters of kPendFilterWords words (vh_alloc.hip: pend_maybe)
+    DevBuf<uint32_t> maskBuf2;             // pipelined multi-camera frames: the camera masks of the second compact buffer
     int genFramesPerLaunch = 4;            // option "gen_frames_per_launch": frames of a batch one key-generation launch takes (1..8)
     uint32_t spinLimit = 0;                // option "spin_limit": polls a workgroup of a serialised pipelined launch waits for the pending commit phase (0: kSpinLimitDefault)
     int pipelineOverflow = 1;              // option "pipeline_overflow": one-launch (serialised) frames with the overflow list: 0 never, 1 by the launch's size (default), 2 always
@@ -159,14 +201,13 @@ struct vh_context {
     MultiPending multiPend;                // the multi-camera frame whose commit + TSDF update have not been launched yet
     void *multiFirstEvent = nullptr;       // hipEvent_t recorded behind the first launch of every vh_apply_frames_batch (vh_dist: the previous batch's packets are free)
     VoxelEntry *compactHome = nullptr;     // the compact buffer of creation: what PtrContainer names, where settle() leaves the dense list
-    float *planeBuf[2] = {nullptr, nullptr};
-    uint16_t *rawBuf[2] = {nullptr, nullptr};
+    DevBuf<float> planeBuf[2];
+    DevBuf<uint16_t> rawBuf[2];
     int occupiedCounter = kCompactCount;   // which device counter holds the occupied count of the last frame
     // raycast over shards
-    void *viewSet = nullptr;               // vh_export_views_fixed: the prepared views (ViewSet) in device memory
-    int32_t *viewLists = nullptr;          // export: selected entry indices, [views][capacity]
-    size_t viewListsSize = 0;              // in int32
-    int32_t *blockList = nullptr;          // vh_render_blocks: two counter words (4 ints) + the records of the allocated blocks
+    DevBuf<ViewSet> viewSet;               // vh_export_views_fixed: the prepared views in device memory
+    DevBuf<int32_t> viewLists;             // export: selected entry indices, [views][capacity]
+    DevBuf<int32_t> blockList;             // vh_render_blocks: two counter words (4 ints) + the records of the allocated blocks
     size_t blockCapacity = 0;              // records blockList has room for
     int foldA = -1, foldB = -1, foldNew = -1;   // counters of the last frame's two-ended compact list while it is unfolded (foldA < 0: dense)
     int blockParity = 0;                   // which counter word the next vh_render_blocks appends through
@@ -300,47 +341,6 @@ static int flush_single_pending(vh_context *c);
 static int flush_multi_pending(vh_context *c);     // vh_api_shard.hip: the same for a multi-camera frame (pipeline_shards 2)
 static int settle(vh_context *c);              // ... and folds a two-ended compact list into the dense one (observers)
 
-static int free_buffers(vh_context *c)
-{
-    // the second buffer set of the pipelined frames (set 0 aliases dp.claim / dp.candidates / dp.compact of creation)
-    for (int i = 0; i < 2; ++i) {
-        if (c->claimBuf[i] && c->claimBuf[i] != c->dp.claim) (void)hipFree(c->claimBuf[i]);
-        if (c->candBuf[i] && c->candBuf[i] != c->dp.candidates) (void)hipFree(c->candBuf[i]);
-        if (c->compactBuf[i] && c->compactBuf[i] != c->dp.compact) (void)hipFree(c->compactBuf[i]);
-        if (c->planeBuf[i]) (void)hipFree(c->planeBuf[i]);
-        if (c->rawBuf[i]) (void)hipFree(c->rawBuf[i]);
-        c->claimBuf[i] = nullptr; c->candBuf[i] = nullptr; c->compactBuf[i] = nullptr;
-        c->planeBuf[i] = nullptr; c->rawBuf[i] = nullptr;
-    }
-    if (c->dp.heap) (void)hipFree(c->dp.heap);
-    if (c->dp.table) (void)hipFree(c->dp.table);
-    if (c->dp.compact) (void)hipFree(c->dp.compact);
-    if (c->dp.claim) (void)hipFree(c->dp.claim);
-    if (c->dp.blocks) (void)hipFree(c->dp.blocks);
-    if (c->dp.counters) (void)hipFree(c->dp.counters);
-    if (c->dp.candidates) (void)hipFree(c->dp.candidates);
-    if (c->dp.candTarget) (void)hipFree(c->dp.candTarget);
-    if (c->dp.gcMarks) (void)hipFree(c->dp.gcMarks);
-    if (c->dp.compactMask) (void)hipFree(c->dp.compactMask);
-    if (c->dp.bucketBits) (void)hipFree(c->dp.bucketBits);
-    if (c->dp.macroBits) (void)hipFree(c->dp.macroBits);
-    if (c->fusedPlane) (void)hipFree(c->fusedPlane);
-    c->fusedPlane = nullptr;
-    if (c->maskBuf2) (void)hipFree(c->maskBuf2);
-    c->maskBuf2 = nullptr;
-    if (c->claimFilter) (void)hipFree(c->claimFilter);
-    c->claimFilter = nullptr;
-    if (c->viewSet) (void)hipFree(c->viewSet);
-    c->viewSet = nullptr;
-    if (c->viewLists) (void)hipFree(c->viewLists);
-    if (c->blockList) (void)hipFree(c->blockList);
-    c->blockList = nullptr;
-    c->viewLists = nullptr;
-    c->viewListsSize = 0;
-    c->dp = DevPtrs{};
-    return VH_OK;
-}
-
 static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_context **out)
 {
     if (!cfg || !out) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
@@ -368,6 +368,7 @@ static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_contex
     c->device = dev;
     DeviceGuard guard(dev);
     if (!guard.ok) { delete c; return fail(VH_ERR_NO_DEVICE, "hipSetDevice"); }
+    // (from here on every `delete c` runs inside the guard's scope: the owners free with c's device current)
     c->params = p;
     c->params.numOccupiedBlocks = 0;
     FrameParams &fp = c->fp;
@@ -399,34 +400,26 @@ static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_contex
     // frames (C3: launch 1 76.2 -> 70.2 us, launch 2 13.5 -> 11.7 us); a resident table (C2, 105 MB) loses
     // 2 % with them.  Option "walk_nt" overrides.
     if (c->numEntries * sizeof(VoxelEntry) > ((size_t)256 << 20)) fp.flags |= kFlagWalkNt;
-    fp.flags |= kFlagWalkShort;          // 4 entries per lane in the frame's walk (option "walk_entries": 4 | 8)
+    fp.flags |= kFlagWalkShort;          // 4 entries per lane in the frame's walk
     const size_t npix = (size_t)cfg->width * cfg->height;
     DevPtrs &dp = c->dp;
     dp = DevPtrs{};
     dp.candCapacity = c->candAllocated = (uint32_t)std::min<size_t>(npix, kMaxCandidates);
 
-#define VH_ALLOC(ptr, bytes)                                               \
-    do {                                                                   \
-        hipError_t e_ = hipMalloc((void **)&(ptr), (bytes));               \
-        if (e_ != hipSuccess) {                                            \
-            free_buffers(c);                                               \
-            delete c;                                                      \
-            return fail(e_ == hipErrorOutOfMemory ? VH_ERR_OUT_OF_MEMORY : VH_ERR_HIP, "hipMalloc " #ptr, e_); \
-        }                                                                  \
-    } while (0)
-    VH_ALLOC(dp.heap, sizeof(uint32_t) * (size_t)p.numVoxelBlocks);
-    VH_ALLOC(dp.table, sizeof(VoxelEntry) * c->numEntries);
-    VH_ALLOC(dp.compact, sizeof(VoxelEntry) * c->numEntries);
-    VH_ALLOC(dp.claim, sizeof(unsigned long long) * (size_t)c->ownedBuckets);
-    VH_ALLOC(dp.blocks, sizeof(Voxel) * (size_t)p.numVoxelBlocks * kBlockVoxels);
-    VH_ALLOC(dp.counters, sizeof(int32_t) * kNumCounters);
-    VH_ALLOC(dp.candidates, sizeof(int4) * npix);
-    VH_ALLOC(dp.candTarget, sizeof(uint32_t) * npix);
-    VH_ALLOC(dp.gcMarks, sizeof(uint32_t) * ((c->numEntries + 31) / 32));
-    VH_ALLOC(dp.compactMask, sizeof(uint32_t) * c->numEntries);
-    VH_ALLOC(dp.bucketBits, sizeof(uint32_t) * (((size_t)c->ownedBuckets + 31) / 32 + 1));   // (+1: the DDA raycast reads it with 8-byte loads)
-    VH_ALLOC(dp.macroBits, kMacroBits / 8);
-#undef VH_ALLOC
+    int rc;
+    if ((rc = c->heap.alloc(p.numVoxelBlocks, "heap")) || (rc = c->table.alloc(c->numEntries, "table")) ||
+        (rc = c->compact[0].alloc(c->numEntries, "compact")) || (rc = c->claim[0].alloc(c->ownedBuckets, "claim")) ||
+        (rc = c->blocks.alloc((size_t)p.numVoxelBlocks * kBlockVoxels, "blocks")) || (rc = c->counters.alloc(kNumCounters, "counters")) ||
+        (rc = c->candidates[0].alloc(npix, "candidates")) || (rc = c->candTarget.alloc(npix, "candTarget")) ||
+        (rc = c->gcMarks.alloc((c->numEntries + 31) / 32, "gcMarks")) || (rc = c->compactMask.alloc(c->numEntries, "compactMask")) ||
+        (rc = c->bucketBits.alloc(((size_t)c->ownedBuckets + 31) / 32 + 1, "bucketBits")) ||   // (+1: the DDA raycast reads it with 8-byte loads)
+        (rc = c->macroBits.alloc(kMacroBits / 32, "macroBits"))) {
+        delete c;
+        return rc;
+    }
+    dp.heap = c->heap; dp.table = c->table; dp.compact = c->compact[0]; dp.claim = c->claim[0]; dp.blocks = c->blocks;
+    dp.counters = c->counters; dp.candidates = c->candidates[0]; dp.candTarget = c->candTarget; dp.gcMarks = c->gcMarks;
+    dp.compactMask = c->compactMask; dp.bucketBits = c->bucketBits; dp.macroBits = c->macroBits;
 
     // deviceAllocate, VoxelUtils.cu:183-208 (+ the compact table and the zeroed
     // volume the reference leaves to OpenGL)
@@ -447,7 +440,6 @@ static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_contex
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) {
-        free_buffers(c);
         delete c;
         return fail(VH_ERR_HIP, "table initialisation", e);
     }
@@ -482,8 +474,7 @@ extern "C" int vh_destroy(vh_context *c)
     // language binding destroys the context late (interpreter exit)
     (void)hipDeviceSynchronize();
     drop_events(c);
-    free_buffers(c);
-    delete c;
+    delete c;                          // the owners free here, behind the synchronise and before the guard restores the device
     return VH_OK;
 }
 
@@ -543,28 +534,21 @@ static int ensure_candidates(vh_context *c, size_t need)
     int rc = flush_pending(c);
     if (rc != VH_OK) return rc;
     VH_HIP(hipStreamSynchronize(c->stream));
-    int4 *fresh = nullptr, *fresh2 = nullptr;
-    uint32_t *freshTarget = nullptr;
     const bool two = c->candBuf[0] != nullptr;               // the pipelined frames' second list
-    hipError_t e = hipMalloc((void **)&fresh, sizeof(int4) * need);
-    if (e == hipSuccess) e = hipMalloc((void **)&freshTarget, sizeof(uint32_t) * need);
-    if (e == hipSuccess && two) e = hipMalloc((void **)&fresh2, sizeof(int4) * need);
-    if (e != hipSuccess) {
-        if (fresh) (void)hipFree(fresh);
-        if (freshTarget) (void)hipFree(freshTarget);
-        return fail(VH_ERR_OUT_OF_MEMORY, "hipMalloc candidate list", e);
-    }
+    DevBuf<int4> fresh, fresh2;                              // (committed only when all of them exist)
+    DevBuf<uint32_t> freshTarget;
+    if ((rc = fresh.alloc(need, "candidate list")) || (rc = freshTarget.alloc(need, "candidate list")) ||
+        (two && (rc = fresh2.alloc(need, "candidate list"))))
+        return rc;
+    c->candidates[0] = std::move(fresh);
+    c->candTarget = std::move(freshTarget);
     if (two) {
-        (void)hipFree(c->candBuf[0]);
-        (void)hipFree(c->candBuf[1]);
-        c->candBuf[0] = fresh;
-        c->candBuf[1] = fresh2;
-    } else {
-        (void)hipFree(c->dp.candidates);
+        c->candidates[1] = std::move(fresh2);
+        c->candBuf[0] = c->candidates[0];
+        c->candBuf[1] = c->candidates[1];
     }
-    (void)hipFree(c->dp.candTarget);
-    c->dp.candidates = fresh;
-    c->dp.candTarget = freshTarget;
+    c->dp.candidates = c->candidates[0];
+    c->dp.candTarget = c->candTarget;
     c->dp.candCapacity = c->candAllocated = (uint32_t)need;
     return VH_OK;
 }

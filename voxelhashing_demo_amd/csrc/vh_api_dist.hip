@@ -190,17 +190,16 @@ struct vh_dist {
     static constexpr int kSets = 4, kSetsSeparate = 3;
     hipEvent_t generated[kSets] = {}, ready[kSets] = {}, first[kSets] = {};     // first: behind the first launch of the set's frames
     struct Set {
-        int32_t *binsSend = nullptr, *binsRecv = nullptr;      // [world][batch][capacity][4]
-        float *packet = nullptr, *packets = nullptr;          // [batch][P], [world][batch][P]
+        DevBuf<int32_t> binsSend, binsRecv;                    // [world][batch][capacity][4]
+        DevBuf<float> packet, packets;                        // [batch][P], [world][batch][P]
     } set[kSets];
     uint64_t count = 0;                    // exchanges fed
     int pending = -1;                      // buffer set whose exchange is in flight / landed but not applied
     // raycast round
-    float *poseMine = nullptr, *poseAll = nullptr;
-    vh_view_record *viewSend = nullptr, *viewRecv = nullptr;
-    int32_t *viewCounts = nullptr;
-    int32_t viewCapacity = 0;
-    int32_t *lostDev = nullptr;            // vh_dist_raycast_auto: [0] this view's lost records, [1..R] every rank's
+    DevBuf<float> poseMine, poseAll;
+    DevBuf<vh_view_record> viewSend, viewRecv;     // [world][capacity] slots each
+    DevBuf<int32_t> viewCounts;
+    DevBuf<int32_t> lostDev;               // vh_dist_raycast_auto: [0] this view's lost records, [1..R] every rank's
     int32_t autoCapacity = 0;              // ... and the slot capacity that last rendered every view whole
     int32_t autoStart = 4096;              // option "raycast_auto_start": this rank's proposal for the first round (the ranks take the largest)
     double hostSeconds = 0.0;
@@ -321,18 +320,16 @@ static int loop_join(vh_dist *d, const char id[VH_DIST_ID_BYTES])
 static void dist_free(vh_dist *d)
 {
     if (!d) return;
+    // The order is explicit, not left to vh_dist's member destructors: this device current, everything on it finished, the view
+    // and shard contexts, the buffers, the events, the transport, and the streams last; `delete d` then finds every owner empty.
     DeviceGuard guard(d->device);
     (void)hipDeviceSynchronize();
     if (d->view) vh_destroy(d->view);
     if (d->shard) vh_destroy(d->shard);
-    for (auto &s : d->set) {
-        if (s.binsSend) (void)hipFree(s.binsSend);
-        if (s.binsRecv) (void)hipFree(s.binsRecv);
-        if (s.packet) (void)hipFree(s.packet);
-        if (s.packets) (void)hipFree(s.packets);
-    }
-    for (void *p : {(void *)d->poseMine, (void *)d->poseAll, (void *)d->viewSend, (void *)d->viewRecv, (void *)d->viewCounts, (void *)d->lostDev})
-        if (p) (void)hipFree(p);
+    for (auto &s : d->set) s = vh_dist::Set{};
+    for (DevBuf<float> *b : {&d->poseMine, &d->poseAll}) b->reset();
+    for (DevBuf<int32_t> *b : {&d->viewCounts, &d->lostDev}) b->reset();
+    for (DevBuf<vh_view_record> *b : {&d->viewSend, &d->viewRecv}) b->reset();
     for (int i = 0; i < vh_dist::kSets; ++i)
         for (hipEvent_t e : {d->generated[i], d->ready[i], d->first[i]})
             if (e) (void)hipEventDestroy(e);
@@ -379,6 +376,39 @@ extern "C" int vh_dist_probe(void)
 
 extern "C" const char *vh_dist_transport_name(vh_dist *d) { return d && d->transport ? d->transport->name : ""; }
 
+// Streams, events and the exchange buffers of a fresh vh_dist.  It may return at any point: the caller's dist_free releases
+// whatever exists by then.
+static int dist_create_resources(vh_dist *d, size_t binWords, size_t pkUnits)
+{
+    const size_t R = (size_t)d->cfg.world;
+    // (Round 4: the key-generation stream restricted to every 2nd / 4th / 8th CU with hipExtStreamCreateWithCUMask, so that the
+    // generation of exchange n+1 would not slow the frame launch it runs beside (28 instead of 20 us): 43.9 / 43.4 / 43.2 k
+    // frames/s against 43.8 k without a mask, the launch as slow as before -- what the two kernels contend for is not CUs.)
+    for (hipStream_t *s : {&d->sGen, &d->sComm, &d->sTable}) VH_HIP(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    for (hipEvent_t *e : {&d->userEvent, &d->outEvent, &d->tableMark}) VH_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (int i = 0; i < vh_dist::kSets; ++i) {
+#ifndef VH_DIST_EVENT_FLAGS_FIRST
+#define VH_DIST_EVENT_FLAGS_FIRST (hipEventDisableTiming | hipEventDisableSystemFence)
+#endif
+#ifndef VH_DIST_EVENT_FLAGS
+#define VH_DIST_EVENT_FLAGS hipEventDisableTiming
+#endif
+        for (hipEvent_t *e : {&d->generated[i], &d->ready[i]}) VH_HIP(hipEventCreateWithFlags(e, VH_DIST_EVENT_FLAGS));
+        // `first` only says that the frames are done READING a buffer set (it orders the next writer on this device behind them),
+        // and it is recorded between two frame launches: no system-scope fence, whose cache write-back the next launch would pay
+        VH_HIP(hipEventCreateWithFlags(&d->first[i], VH_DIST_EVENT_FLAGS_FIRST));
+        vh_dist::Set &set = d->set[i];
+        int rc;
+        if ((rc = set.binsSend.alloc(binWords, "binsSend")) || (rc = set.binsRecv.alloc(binWords, "binsRecv")) ||
+            (rc = set.packet.alloc(pkUnits, "packet")) || (rc = set.packets.alloc(pkUnits * R, "packets")))
+            return rc;
+        VH_HIP(hipMemset(set.binsSend, 0, binWords * sizeof(int32_t)));
+        VH_HIP(hipMemset(set.binsRecv, 0, binWords * sizeof(int32_t)));
+    }
+    VH_HIP(hipDeviceSynchronize());
+    return VH_OK;
+}
+
 extern "C" int vh_dist_create(const vh_dist_config *cfg, const char id[VH_DIST_ID_BYTES], void *nccl_comm, vh_dist **out)
 {
     if (!cfg || !out || (!id && !nccl_comm)) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
@@ -419,41 +449,8 @@ extern "C" int vh_dist_create(const vh_dist_config *cfg, const char id[VH_DIST_I
     d->capacity = cfg->key_capacity > 0 ? cfg->key_capacity : (int)std::max<size_t>(8192, perOwner + 1);
     d->packetUnits = cfg->packet_format == VH_PACKET_U16 ? (size_t)kPacketHeaderU16 + npix / 2 : (size_t)kPacketHeader + npix;
     const size_t B = (size_t)cfg->batch;
-    const size_t binBytes = (size_t)R * (size_t)d->capacity * 4 * sizeof(int32_t);      // [peer][capacity] records of 16 bytes
-    const size_t pkBytes = B * d->packetUnits * sizeof(float);
-#define VH_DIST_TRY(call)                                                                            \
-    do {                                                                                             \
-        const hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                      \
-            dist_free(d);                                                                            \
-            return fail(e_ == hipErrorOutOfMemory ? VH_ERR_OUT_OF_MEMORY : VH_ERR_HIP, #call, e_);   \
-        }                                                                                            \
-    } while (0)
-    // (Round 4: the key-generation stream restricted to every 2nd / 4th / 8th CU with hipExtStreamCreateWithCUMask, so that the
-    // generation of exchange n+1 would not slow the frame launch it runs beside (28 instead of 20 us): 43.9 / 43.4 / 43.2 k
-    // frames/s against 43.8 k without a mask, the launch as slow as before -- what the two kernels contend for is not CUs.)
-    for (hipStream_t *s : {&d->sGen, &d->sComm, &d->sTable}) VH_DIST_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
-    for (hipEvent_t *e : {&d->userEvent, &d->outEvent, &d->tableMark}) VH_DIST_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    for (int i = 0; i < vh_dist::kSets; ++i) {
-#ifndef VH_DIST_EVENT_FLAGS_FIRST
-#define VH_DIST_EVENT_FLAGS_FIRST (hipEventDisableTiming | hipEventDisableSystemFence)
-#endif
-#ifndef VH_DIST_EVENT_FLAGS
-#define VH_DIST_EVENT_FLAGS hipEventDisableTiming
-#endif
-        for (hipEvent_t *e : {&d->generated[i], &d->ready[i]}) VH_DIST_TRY(hipEventCreateWithFlags(e, VH_DIST_EVENT_FLAGS));
-        // `first` only says that the frames are done READING a buffer set (it orders the next writer on this device behind them),
-        // and it is recorded between two frame launches: no system-scope fence, whose cache write-back the next launch would pay
-        VH_DIST_TRY(hipEventCreateWithFlags(&d->first[i], VH_DIST_EVENT_FLAGS_FIRST));
-        VH_DIST_TRY(hipMalloc((void **)&d->set[i].binsSend, binBytes));
-        VH_DIST_TRY(hipMalloc((void **)&d->set[i].binsRecv, binBytes));
-        VH_DIST_TRY(hipMalloc((void **)&d->set[i].packet, pkBytes));
-        VH_DIST_TRY(hipMalloc((void **)&d->set[i].packets, pkBytes * R));
-        VH_DIST_TRY(hipMemset(d->set[i].binsSend, 0, binBytes));
-        VH_DIST_TRY(hipMemset(d->set[i].binsRecv, 0, binBytes));
-    }
-    VH_DIST_TRY(hipDeviceSynchronize());
-#undef VH_DIST_TRY
+    const size_t binWords = (size_t)R * (size_t)d->capacity * 4;      // [peer][capacity] records of 16 bytes
+    if ((rc = dist_create_resources(d, binWords, B * d->packetUnits)) != VH_OK) { dist_free(d); return rc; }
     if (loopback) {
         if ((rc = loop_join(d, id)) != VH_OK) { dist_free(d); return rc; }
         d->transport = &kLoopTransport;
@@ -586,14 +583,14 @@ extern "C" int vh_dist_self_check(vh_dist *d)
     const uint32_t words = (uint32_t)std::min<size_t>(16384, std::min<size_t>((size_t)d->capacity * 4, (size_t)d->cfg.batch * d->packetUnits)) & ~255u;
     if (words == 0) return fail(VH_ERR_INVALID_ARGUMENT, "vh_dist_self_check: exchange buffers smaller than 1 KB");
     vh_dist::Set &set = d->set[0];
-    int32_t *bad = nullptr;
-    VH_HIP(hipMalloc((void **)&bad, sizeof(int32_t)));
+    DevBuf<int32_t> bad;                           // (a local: freed on every return below, under this call's guard)
+    if ((rc = bad.alloc(1, "self-check word")) != VH_OK) return rc;
     VH_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), d->sComm));
-    dist_pattern_kernel<<<dim3(words / 256), dim3(256), 0, d->sComm>>>(reinterpret_cast<uint32_t *>(set.binsSend), reinterpret_cast<uint32_t *>(set.packet), d->cfg.rank, R, words);
+    dist_pattern_kernel<<<dim3(words / 256), dim3(256), 0, d->sComm>>>(reinterpret_cast<uint32_t *>(set.binsSend.get()), reinterpret_cast<uint32_t *>(set.packet.get()), d->cfg.rank, R, words);
     rc = d->transport->all_to_all(d, set.binsSend, set.binsRecv, (size_t)words * 4, d->sComm);
     if (rc == VH_OK) rc = d->transport->all_gather(d, set.packet, set.packets, (size_t)words * 4, d->sComm);
-    if (rc != VH_OK) { (void)hipFree(bad); return rc; }
-    dist_pattern_check_kernel<<<dim3(words / 256), dim3(256), 0, d->sComm>>>(reinterpret_cast<const uint32_t *>(set.binsRecv), reinterpret_cast<const uint32_t *>(set.packets), d->cfg.rank, R, words, bad);
+    if (rc != VH_OK) return rc;
+    dist_pattern_check_kernel<<<dim3(words / 256), dim3(256), 0, d->sComm>>>(reinterpret_cast<const uint32_t *>(set.binsRecv.get()), reinterpret_cast<const uint32_t *>(set.packets.get()), d->cfg.rank, R, words, bad.get());
     int32_t n = -1;
     hipError_t e = hipMemcpyAsync(&n, bad, sizeof n, hipMemcpyDeviceToHost, d->sComm);
     if (e == hipSuccess) e = hipStreamSynchronize(d->sComm);
@@ -602,7 +599,6 @@ extern "C" int vh_dist_self_check(vh_dist *d)
     if (e == hipSuccess) e = hipMemsetAsync(set.binsSend, 0, binBytes, d->sComm);
     if (e == hipSuccess) e = hipMemsetAsync(set.binsRecv, 0, binBytes, d->sComm);
     if (e == hipSuccess) e = hipStreamSynchronize(d->sComm);
-    (void)hipFree(bad);
     if (e != hipSuccess) return fail(VH_ERR_HIP, "vh_dist_self_check", e);
     if (n == 0 && late != VH_OK) return late;
     if (n != 0) {
@@ -673,11 +669,11 @@ static int dist_step_fused(vh_dist *d, const float *poses, const void *const *d_
             j.unit = 5000.0f;                                                                       // CameraTrackingUtils.cu:64
             j.blocks = (tiles + kFusedGenGroups - 1) / kFusedGenGroups;
             j.numShards = R; j.capacity = d->capacity; j.binStride = d->capacity;
-            j.bins = reinterpret_cast<int4 *>(set.binsSend);
+            j.bins = reinterpret_cast<int4 *>(set.binsSend.get());
             j.packet = set.packet + (size_t)b * d->packetUnits;
             j.depth = reinterpret_cast<const uint16_t *>(d_frames[b]);
             j.rankBase = (uint32_t)b << kRankCameraShift;
-            if (b == B - 1) { j.clearBins = reinterpret_cast<int4 *>(d->set[sNext].binsSend); j.clearStride = d->capacity; }
+            if (b == B - 1) { j.clearBins = reinterpret_cast<int4 *>(d->set[sNext].binsSend.get()); j.clearStride = d->capacity; }
             j.frame = b; j.batch = B;
         }
     } else {
@@ -706,7 +702,7 @@ static int dist_step_fused(vh_dist *d, const float *poses, const void *const *d_
         if (canFuse) {
             if (d->haveUser) VH_HIP(hipStreamWaitEvent(d->sTable, d->userEvent, 0));
             if (!d->headersClean[s]) {      // (the first fused call behind a separate one: nobody has emptied this set's send bins)
-                prepare_bins_fused_kernel<<<1, 64, 0, d->sTable>>>(reinterpret_cast<int4 *>(set.binsSend), R, d->capacity, d->capacity, B);
+                prepare_bins_fused_kernel<<<1, 64, 0, d->sTable>>>(reinterpret_cast<int4 *>(set.binsSend.get()), R, d->capacity, d->capacity, B);
             }
         }
         if ((rc = dist_apply(d, old, canFuse ? jobs : nullptr)) != VH_OK) return rc;
@@ -878,10 +874,11 @@ static int dist_raycast_impl(vh_dist *d, const float pose[16], float t_min, floa
         vc.device = d->device;
         if ((rc = vh_create(&vc, &d->view)) != VH_OK) return rc;
         d->view->stream = d->sTable;
-        VH_HIP(hipMalloc((void **)&d->poseMine, 16 * sizeof(float)));
-        VH_HIP(hipMalloc((void **)&d->poseAll, (size_t)R * 16 * sizeof(float)));
-        VH_HIP(hipMalloc((void **)&d->viewCounts, (size_t)R * sizeof(int32_t)));
     }
+    // (tested buffer by buffer, not by d->view: a call that failed half-way here is completed by the next one; no-ops afterwards)
+    if ((rc = d->poseMine.reserve(16, "poseMine")) || (rc = d->poseAll.reserve((size_t)R * 16, "poseAll")) ||
+        (rc = d->viewCounts.reserve((size_t)R, "viewCounts")))
+        return rc;
     // the view table renders with the shard's raycast settings as they are NOW (vh_set_option / vh_set_raycast_intrinsics
     // on vh_dist_shard() between rounds take effect)
     d->view->rc_fx = d->shard->rc_fx; d->view->rc_fy = d->shard->rc_fy; d->view->rc_cx = d->shard->rc_cx; d->view->rc_cy = d->shard->rc_cy;
@@ -889,18 +886,12 @@ static int dist_raycast_impl(vh_dist *d, const float pose[16], float t_min, floa
     d->view->raycastBeam = d->shard->raycastBeam;
     d->view->fp.flags = (d->view->fp.flags & ~kFlagOverflow) | (d->shard->fp.flags & kFlagOverflow);
     d->view->fp.listSize = d->shard->fp.listSize;
-    if (d->viewCapacity < capacity) {
+    const size_t slots = (size_t)R * capacity;
+    if (d->viewSend.size() < slots || d->viewRecv.size() < slots) {     // (a half-grown pair is completed by the next call)
         VH_HIP(hipStreamSynchronize(d->sTable));
-        if (d->viewSend) (void)hipFree(d->viewSend);
-        if (d->viewRecv) (void)hipFree(d->viewRecv);
-        d->viewSend = d->viewRecv = nullptr;
-        d->viewCapacity = 0;
-        const size_t bytes = (size_t)R * capacity * sizeof(vh_view_record);
-        VH_HIP(hipMalloc((void **)&d->viewSend, bytes));
-        VH_HIP(hipMalloc((void **)&d->viewRecv, bytes));
-        VH_HIP(hipMemsetAsync(d->viewSend, 0, bytes, d->sTable));
-        VH_HIP(hipMemsetAsync(d->viewRecv, 0, bytes, d->sTable));
-        d->viewCapacity = capacity;
+        if ((rc = d->viewSend.reserve(slots, "viewSend")) || (rc = d->viewRecv.reserve(slots, "viewRecv"))) return rc;
+        VH_HIP(hipMemsetAsync(d->viewSend, 0, slots * sizeof(vh_view_record), d->sTable));
+        VH_HIP(hipMemsetAsync(d->viewRecv, 0, slots * sizeof(vh_view_record), d->sTable));
     }
     // the image (and d_lost) are written behind whatever the caller's stream has queued, and the caller's stream reads them
     // behind the raycast (vh_dist_set_user_stream)
@@ -919,7 +910,7 @@ static int dist_raycast_impl(vh_dist *d, const float pose[16], float t_min, floa
     rc = d_normals_out ? vh_raycast_normals(d->view, pose, t_min, t_max, d_depth_out, d_normals_out)
                        : vh_raycast(d->view, pose, t_min, t_max, d_depth_out);
     if (rc != VH_OK) return rc;
-    if (d_lost) dist_lost_kernel<<<1, 64, 0, d->sTable>>>(reinterpret_cast<const uint8_t *>(d->viewRecv), R, capacity, d_lost);
+    if (d_lost) dist_lost_kernel<<<1, 64, 0, d->sTable>>>(reinterpret_cast<const uint8_t *>(d->viewRecv.get()), R, capacity, d_lost);
     VH_HIP(hipGetLastError());
     if (d->haveUser) {
         VH_HIP(hipEventRecord(d->outEvent, d->sTable));
@@ -942,9 +933,12 @@ extern "C" int vh_dist_raycast_auto(vh_dist *d, const float pose[16], float t_mi
     if (!d) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
     DeviceGuard guard(d->device);
     const int R = d->cfg.world;
-    if (!d->lostDev) {
-        VH_HIP(hipMalloc((void **)&d->lostDev, sizeof(int32_t) * (size_t)(R + 1)));
-        VH_HIP(hipMemset(d->lostDev, 0, sizeof(int32_t) * (size_t)(R + 1)));
+    if (!d->lostDev) {                                  // all or nothing: committed behind the memset
+        DevBuf<int32_t> fresh;
+        const int rc = fresh.alloc((size_t)(R + 1), "lostDev");
+        if (rc != VH_OK) return rc;
+        VH_HIP(hipMemset(fresh, 0, sizeof(int32_t) * (size_t)(R + 1)));
+        d->lostDev = std::move(fresh);
     }
     // a shard cannot select more blocks than its pool holds, and the view table lists one imported record per entry
     const int64_t most = std::max<int64_t>(1, std::min<int64_t>((int64_t)d->cfg.table.params.numVoxelBlocks,

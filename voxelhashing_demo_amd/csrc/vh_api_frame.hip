@@ -193,35 +193,31 @@ static int ensure_pipeline_buffers(vh_context *c)
     if (c->claimBuf[1]) return VH_OK;
     const size_t npix = (size_t)c->fp.width * c->fp.height;
     const size_t claimBytes = sizeof(unsigned long long) * (size_t)c->ownedBuckets;
-    unsigned long long *claim2 = nullptr;
-    int4 *cand2 = nullptr;
-    VoxelEntry *compact2 = nullptr;
-    uint32_t *filter = nullptr;
-    float *plane[2] = {nullptr, nullptr};
-    uint16_t *raw[2] = {nullptr, nullptr};
-    hipError_t e = hipMalloc((void **)&claim2, claimBytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&cand2, sizeof(int4) * (size_t)c->candAllocated);
-    if (e == hipSuccess) e = hipMalloc((void **)&compact2, sizeof(VoxelEntry) * c->numEntries);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc((void **)&plane[i], sizeof(float) * npix);
-        if (e == hipSuccess) e = hipMalloc((void **)&raw[i], sizeof(uint16_t) * npix);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(claim2, 0, claimBytes, c->stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&filter, sizeof(uint32_t) * 3 * kPendFilterWords);
-    if (e == hipSuccess) e = hipMemsetAsync(filter, 0, sizeof(uint32_t) * 3 * kPendFilterWords, c->stream);
-    if (e != hipSuccess) {
-        if (filter) (void)hipFree(filter);
-        if (claim2) (void)hipFree(claim2);
-        if (cand2) (void)hipFree(cand2);
-        if (compact2) (void)hipFree(compact2);
-        for (int i = 0; i < 2; ++i) { if (plane[i]) (void)hipFree(plane[i]); if (raw[i]) (void)hipFree(raw[i]); }
-        return fail(e == hipErrorOutOfMemory ? VH_ERR_OUT_OF_MEMORY : VH_ERR_HIP, "pipeline buffers", e);
-    }
-    c->claimBuf[0] = c->dp.claim;          c->claimBuf[1] = claim2;
-    c->candBuf[0] = c->dp.candidates;      c->candBuf[1] = cand2;
-    c->compactBuf[0] = c->dp.compact;      c->compactBuf[1] = compact2;
-    for (int i = 0; i < 2; ++i) { c->planeBuf[i] = plane[i]; c->rawBuf[i] = raw[i]; }
-    c->claimFilter = filter;
+    // all or nothing: allocated into locals, which free themselves on any early return; the context is written from the commit on
+    DevBuf<unsigned long long> claim2;
+    DevBuf<int4> cand2;
+    DevBuf<VoxelEntry> compact2;
+    DevBuf<uint32_t> filter;
+    DevBuf<float> plane[2];
+    DevBuf<uint16_t> raw[2];
+    int rc;
+    if ((rc = claim2.alloc(c->ownedBuckets, "pipeline buffers")) || (rc = cand2.alloc(c->candAllocated, "pipeline buffers")) ||
+        (rc = compact2.alloc(c->numEntries, "pipeline buffers")) ||
+        (rc = plane[0].alloc(npix, "pipeline buffers")) || (rc = raw[0].alloc(npix, "pipeline buffers")) ||
+        (rc = plane[1].alloc(npix, "pipeline buffers")) || (rc = raw[1].alloc(npix, "pipeline buffers")))
+        return rc;
+    VH_HIP(hipMemsetAsync(claim2, 0, claimBytes, c->stream));
+    if ((rc = filter.alloc(3 * kPendFilterWords, "pipeline buffers")) != VH_OK) return rc;
+    VH_HIP(hipMemsetAsync(filter, 0, sizeof(uint32_t) * 3 * kPendFilterWords, c->stream));
+    // commit
+    c->claim[1] = std::move(claim2);
+    c->candidates[1] = std::move(cand2);
+    c->compact[1] = std::move(compact2);
+    for (int i = 0; i < 2; ++i) { c->planeBuf[i] = std::move(plane[i]); c->rawBuf[i] = std::move(raw[i]); }
+    c->claimFilter = std::move(filter);
+    c->claimBuf[0] = c->dp.claim;          c->claimBuf[1] = c->claim[1];
+    c->candBuf[0] = c->dp.candidates;      c->candBuf[1] = c->candidates[1];
+    c->compactBuf[0] = c->dp.compact;      c->compactBuf[1] = c->compact[1];
     c->pipeParity = 0;                     // dp.* currently alias set 0
     return VH_OK;
 }
@@ -297,15 +293,15 @@ static int launch_pipelined(vh_context *c, const In *in, int newSensor, const fl
     a.commitBlocks = hasOld ? (uint32_t)c->commitBlocks : 0u;
     a.integrateBlocks = hasOld ? (uint32_t)c->pipeIntegrateGrid : 0u;
     // (the walk-free frame of a large image: its TSDF update is on the critical path, not under a walk -- twice the workgroups:
-    // C3 26.1 -> 25.1 us, while C2 prefers the 512 it has, 8.7 against 9.0; option "pipe_integrate_grid" sets the base)
+    // C3 26.1 -> 25.1 us, while C2 prefers the 512 it has, 8.7 against 9.0)
     if (hasOld && a.walkIndexed && host_num_tiles(c) > 2400u) a.integrateBlocks *= 2u;
     a.numEntries = (uint32_t)c->numEntries;
     a.setNew = kPipeSetStride * setNew; a.setOld = kPipeSetStride * setOld; a.setClear = kPipeSetStride * ((setNew + 1) % 3);
     a.hasNew = hasNew; a.hasOld = hasOld;
     a.claimSpan = claim_span(c, a.claimBlocks, a.walkBlocks);
     a.claimRatio = claim_ratio(a.claimBlocks, a.claimSpan);
-    a.planeNew = (hasNew && !newSensor) ? c->planeBuf[newParity] : nullptr;
-    a.rawNew = (hasNew && newSensor) ? c->rawBuf[newParity] : nullptr;
+    a.planeNew = (hasNew && !newSensor) ? c->planeBuf[newParity].get() : nullptr;
+    a.rawNew = (hasNew && newSensor) ? c->rawBuf[newParity].get() : nullptr;
     a.filter = c->claimFilter;
     a.filtNew = kPendFilterWords * (uint32_t)setNew; a.filtOld = kPendFilterWords * (uint32_t)setOld;
     a.filtClear = kPendFilterWords * (uint32_t)((setNew + 1) % 3);
@@ -429,8 +425,8 @@ static int launch_scan_claim(vh_context *c, const In &in, uint32_t claimBlocks, 
 // the packed camera-z plane launch 1 leaves for launch 2 (vertex-map input only)
 static inline float *fused_plane(vh_context *c, const VertexMap &)
 {
-    if (!c->fusedPlane && hipMalloc((void **)&c->fusedPlane, sizeof(float) * (size_t)c->fp.width * c->fp.height) != hipSuccess)
-        c->fusedPlane = nullptr;                  // (out of memory: launch 2 gathers from the vertex map as before)
+    // optional: a failed allocation leaves it empty (launch 2 gathers from the vertex map as before) and the next frame tries again
+    if (!c->fusedPlane) (void)c->fusedPlane.try_alloc((size_t)c->fp.width * c->fp.height);
     return c->fusedPlane;
 }
 static inline float *fused_plane(vh_context *, const SensorImage &) { return nullptr; }
@@ -676,16 +672,15 @@ extern "C" int vh_render_blocks(vh_context *c, const float pose[16], float t_min
     // numVoxelBlocks of them, a view table one per entry) behind two counter words, allocated on first use (synchronises once)
     const size_t capacity = c->viewBlocks ? c->numEntries : std::min<size_t>(c->numEntries, c->params.numVoxelBlocks);
     if (!c->blockList || c->blockCapacity < capacity) {      // (a view context grows from 1 to numEntries at its first import)
-        VH_HIP(hipStreamSynchronize(c->stream));
-        if (c->blockList) (void)hipFree(c->blockList);
-        c->blockList = nullptr;
-        VH_HIP(hipMalloc((void **)&c->blockList, 16 + (sizeof(BlockRecord) + sizeof(uint2)) * capacity));
+        VH_HIP(hipStreamSynchronize(c->stream));                 // (the caller's stream logic: before the old list is freed)
+        const int arc = c->blockList.alloc(4 + (sizeof(BlockRecord) + sizeof(uint2)) / sizeof(int32_t) * capacity, "blockList");
+        if (arc != VH_OK) return arc;
         VH_HIP(hipMemsetAsync(c->blockList, 0, 16, c->stream));
         c->blockCapacity = capacity;
         c->blockParity = 0;
     }
     int32_t *counts = c->blockList;
-    BlockRecord *records = reinterpret_cast<BlockRecord *>(c->blockList + 4);
+    BlockRecord *records = reinterpret_cast<BlockRecord *>(counts + 4);
     uint2 *bounds = reinterpret_cast<uint2 *>(records + c->blockCapacity);
     const int parity = c->blockParity;
     const uint32_t words = (c->ownedBuckets + 31u) / 32u;

@@ -7,17 +7,17 @@ struct vh_icp {
     int device = 0;
     int width = 0, height = 0;
     hipStream_t stream = nullptr;
-    float *partials = nullptr;     // [blocks][32]
-    IcpState *state = nullptr;     // device-resident Align state
+    DevBuf<float> partials;        // [blocks][32]
+    DevBuf<IcpState> state;        // device-resident Align state
     IcpState *hostState = nullptr; // pinned copy (the one-launch Align writes its result here itself)
     IcpState *hostStateDev = nullptr;   // ... under this address
     int blocks = 0;                // grid of icp_round_kernel
     int alignBlocks = 0, alignSlots = -1;  // grid of icp_align_kernel and pixels per lane it keeps in registers (0: none, the points are
                                            // read again every round); -1: Align is a chain of one-launch rounds
-    unsigned long long *records = nullptr, *pub = nullptr;   // one-launch Align: [alignBlocks][32] sums, [8][16] estimate, each word {value, seq}
+    DevBuf<unsigned long long> records, pub;                 // one-launch Align: [alignBlocks][32] sums, [8][16] estimate, each word {value, seq}
     uint32_t spinLimit = 1u << 20;         // polls (~1 us each) before a workgroup of the one-launch Align gives up; VH_ICP_SPIN_LIMIT
     int seqBase = 0;                       // sequence numbers handed out so far (they only grow: nothing is reset between calls)
-    unsigned long long *stamps = nullptr;  // diagnostics (VH_ICP_STAMPS=1): [round][8] time stamps of the one-launch Align
+    DevBuf<unsigned long long> stamps;     // diagnostics (VH_ICP_STAMPS=1): [round][8] time stamps of the one-launch Align
 };
 
 constexpr int kIcpAlignMaxSlots = 6;
@@ -73,22 +73,20 @@ extern "C" int vh_icp_create(int32_t width, int32_t height, int32_t device, vh_i
             p->alignSlots = -1;
     }
     if (const char *e = std::getenv("VH_ICP_SPIN_LIMIT")) p->spinLimit = (uint32_t)std::max(1, std::atoi(e));   // (tests: 1 = the time-out path)
-    if (std::getenv("VH_ICP_STAMPS")) (void)hipMalloc((void **)&p->stamps, sizeof(unsigned long long) * (512 + 1024));
-    hipError_t e = hipMalloc((void **)&p->partials, sizeof(float) * kIcpStride * (size_t)p->blocks);
-    const size_t recordBytes = sizeof(unsigned long long) * kIcpStride * (size_t)p->alignBlocks;
-    const size_t pubBytes = sizeof(unsigned long long) * kIcpPubCopies * kIcpPubStride;
-    if (e == hipSuccess) e = hipMalloc((void **)&p->records, recordBytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->pub, pubBytes);
-    if (e == hipSuccess) e = hipMemset(p->records, 0, recordBytes);
-    if (e == hipSuccess) e = hipMemset(p->pub, 0, pubBytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->state, sizeof(IcpState));
+    if (std::getenv("VH_ICP_STAMPS")) (void)p->stamps.try_alloc(512 + 1024);      // optional: Align runs without stamps when this fails
+    const size_t recordWords = kIcpStride * (size_t)p->alignBlocks, pubWords = (size_t)kIcpPubCopies * kIcpPubStride;
+    int rc;
+    if ((rc = p->partials.alloc(kIcpStride * (size_t)p->blocks, "icp workspace")) || (rc = p->records.alloc(recordWords, "icp workspace")) ||
+        (rc = p->pub.alloc(pubWords, "icp workspace")) || (rc = p->state.alloc(1, "icp workspace"))) {
+        delete p;                          // (inside the guard's scope: the owners free on p's device)
+        return rc;
+    }
+    hipError_t e = hipMemset(p->records, 0, sizeof(unsigned long long) * recordWords);
+    if (e == hipSuccess) e = hipMemset(p->pub, 0, sizeof(unsigned long long) * pubWords);
     if (e == hipSuccess) e = hipHostMalloc((void **)&p->hostState, sizeof(IcpState), hipHostMallocMapped);
     if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&p->hostStateDev, p->hostState, 0);
     if (e != hipSuccess) {
-        if (p->partials) (void)hipFree(p->partials);
-        if (p->records) (void)hipFree(p->records);
-        if (p->pub) (void)hipFree(p->pub);
-        if (p->state) (void)hipFree(p->state);
+        if (p->hostState) (void)hipHostFree(p->hostState);
         delete p;
         return fail(e == hipErrorOutOfMemory ? VH_ERR_OUT_OF_MEMORY : VH_ERR_HIP, "icp workspace", e);
     }
@@ -112,13 +110,8 @@ extern "C" int vh_icp_destroy(vh_icp *p)
     if (!p) return VH_OK;
     DeviceGuard guard(p->device);
     (void)hipDeviceSynchronize();      // not p->stream: the caller's stream object may already be gone
-    (void)hipFree(p->partials);
-    (void)hipFree(p->records);
-    (void)hipFree(p->pub);
-    (void)hipFree(p->state);
-    if (p->stamps) (void)hipFree(p->stamps);
     (void)hipHostFree(p->hostState);
-    delete p;
+    delete p;                          // the owners free here: behind the synchronise, with p's device current
     return VH_OK;
 }
 
@@ -257,8 +250,8 @@ extern "C" int vh_icp_align(vh_icp *p, const vh_float4 *d_input, const vh_float4
         p->seqBase += max_iters;
         IcpStart start;
         std::memcpy(start.T, T, sizeof start.T);
-        void *args[] = {(void *)&ip, (void *)&in, (void *)&tg, (void *)&tn, (void *)&p->records, (void *)&p->pub, (void *)&start,
-                        (void *)&p->hostStateDev, (void *)&max_iters, (void *)&seqBase, (void *)&spinLimit, (void *)&p->stamps};
+        void *args[] = {(void *)&ip, (void *)&in, (void *)&tg, (void *)&tn, (void *)&p->records.p, (void *)&p->pub.p, (void *)&start,
+                        (void *)&p->hostStateDev, (void *)&max_iters, (void *)&seqBase, (void *)&spinLimit, (void *)&p->stamps.p};
         VH_HIP(hipLaunchKernel(icp_align_entry(p->alignSlots), dim3(p->alignBlocks), dim3(kIcpThreads), args, 0, p->stream));
     } else {
         for (int it = 0; it < max_iters; ++it)

@@ -32,13 +32,10 @@ extern "C" int vh_export_views(vh_context *c, const float *poses, int32_t n_view
     DeviceGuard guard(c->device);
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }
     const size_t need = (size_t)n_views * (size_t)capacity;
-    if (c->viewListsSize < need) {                         // first call (or a larger one): synchronises
+    if (c->viewLists.size() < need) {                      // first call (or a larger one): synchronises
         VH_HIP(hipStreamSynchronize(c->stream));
-        if (c->viewLists) (void)hipFree(c->viewLists);
-        c->viewLists = nullptr;
-        c->viewListsSize = 0;
-        VH_HIP(hipMalloc((void **)&c->viewLists, need * sizeof(int32_t)));
-        c->viewListsSize = need;
+        const int rc = c->viewLists.reserve(need, "viewLists");
+        if (rc != VH_OK) return rc;
     }
     VH_HIP(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * (size_t)n_views, c->stream));
     const uint32_t tiles = (uint32_t)((c->numEntries + kFlattenThreads * kEntriesPerLane - 1) /
@@ -49,12 +46,12 @@ extern "C" int vh_export_views(vh_context *c, const float *poses, int32_t n_view
         std::memset(&vs, 0, sizeof vs);
         for (int32_t v = 0; v < n; ++v) make_view_frustum(c, poses + 16 * (size_t)(base + v), t_min, t_max, vs.v[v].f);
         const int rc = launch(c, kPhaseViewExport, view_select_kernel, dim3(tiles), dim3(kFlattenThreads), c->fp, c->dp,
-                              (uint32_t)c->numEntries, vs, n, c->viewLists + (size_t)base * capacity, capacity,
+                              (uint32_t)c->numEntries, vs, n, c->viewLists.get() + (size_t)base * capacity, capacity,
                               d_counts + base);
         if (rc != VH_OK) return rc;
     }
     const int rc = launch(c, kPhaseViewExport, view_pack_kernel, dim3((unsigned)std::min<int32_t>(capacity, 2048), n_views),
-                          dim3(256), c->dp, (const int32_t *)c->viewLists, (const int32_t *)d_counts, capacity,
+                          dim3(256), c->dp, (const int32_t *)c->viewLists.get(), (const int32_t *)d_counts, capacity,
                           reinterpret_cast<uint8_t *>(d_records), 0);
     if (rc != VH_OK) return rc;
     VH_HIP(hipGetLastError());
@@ -111,29 +108,24 @@ extern "C" int vh_export_views_fixed(vh_context *c, const float *d_poses, int32_
     DeviceGuard guard(c->device);
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }
     const size_t need = (size_t)n_views * (size_t)capacity;
-    if (c->viewListsSize < need || !c->viewSet) {            // first call (or a larger one): synchronises
+    if (c->viewLists.size() < need || !c->viewSet) {         // first call (or a larger one): synchronises
         VH_HIP(hipStreamSynchronize(c->stream));
-        if (c->viewListsSize < need) {
-            if (c->viewLists) (void)hipFree(c->viewLists);
-            c->viewLists = nullptr;
-            c->viewListsSize = 0;
-            VH_HIP(hipMalloc((void **)&c->viewLists, need * sizeof(int32_t)));
-            c->viewListsSize = need;
-        }
-        if (!c->viewSet) VH_HIP(hipMalloc((void **)&c->viewSet, sizeof(ViewSet)));
+        int rc = c->viewLists.reserve(need, "viewLists");        // (each buffer is tested on its own: a failure is retried next call)
+        if (rc == VH_OK) rc = c->viewSet.reserve(1, "viewSet");
+        if (rc != VH_OK) return rc;
     }
     VH_HIP(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * (size_t)n_views, c->stream));
     const ViewCamera cam{c->rc_fx, c->rc_fy, c->rc_cx, c->rc_cy, t_min, t_max, c->fp.width, c->fp.height};
     int rc = launch(c, kPhaseViewExport, view_frustum_kernel, dim3(1), dim3(64), d_poses, n_views, cam, c->fp.voxelSize,
-                    reinterpret_cast<ViewSet *>(c->viewSet));
+                    c->viewSet.get());
     const uint32_t tiles = (uint32_t)((c->numEntries + kFlattenThreads * kEntriesPerLane - 1) /
                                       (kFlattenThreads * kEntriesPerLane));
     if (rc == VH_OK)
         rc = launch(c, kPhaseViewExport, view_select_mem_kernel, dim3(tiles), dim3(kFlattenThreads), c->fp, c->dp,
-                    (uint32_t)c->numEntries, (const ViewSet *)c->viewSet, n_views, c->viewLists, capacity, d_counts);
+                    (uint32_t)c->numEntries, (const ViewSet *)c->viewSet.get(), n_views, c->viewLists.get(), capacity, d_counts);
     if (rc == VH_OK)
         rc = launch(c, kPhaseViewExport, view_pack_kernel, dim3((unsigned)std::min<int32_t>(capacity, 2048), n_views),
-                    dim3(256), c->dp, (const int32_t *)c->viewLists, (const int32_t *)d_counts, capacity,
+                    dim3(256), c->dp, (const int32_t *)c->viewLists.get(), (const int32_t *)d_counts, capacity,
                     reinterpret_cast<uint8_t *>(d_records), 1);
     if (rc != VH_OK) return rc;
     VH_HIP(hipGetLastError());
@@ -558,7 +550,7 @@ static int vh_apply_frames_batch_gen(vh_context *c, int32_t batch, const int32_t
         serial_launch_pays(c, (uint32_t)num_bins * parts + (uint32_t)grid_for(c->numEntries, kFlattenThreads * kEntriesPerLaneShort))) {
         int rc = ensure_pipeline_buffers(c);
         if (rc != VH_OK) return rc;
-        if (!c->maskBuf2) VH_HIP(hipMalloc((void **)&c->maskBuf2, sizeof(uint32_t) * c->numEntries));
+        if ((rc = c->maskBuf2.reserve(c->numEntries, "maskBuf2")) != VH_OK) return rc;      // (first use)
         MultiPending &mp = c->multiPend;
         // a pending half of another shape (camera count, packet layout) cannot share a launch with this batch's frames
         if (mp.active && (mp.numCams != num_cams || mp.packetStride != packet_stride || mp.packetFormat != c->packetFormat) &&

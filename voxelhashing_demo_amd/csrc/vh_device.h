@@ -91,7 +91,7 @@ struct FrameParams {
 constexpr uint32_t kFlagOverflow = 1u;          // overflow linked list (dead code in the reference, :384-411, :458-539, :578-602)
 constexpr uint32_t kFlagBandDda = 2u;           // band allocation by a block DDA along the normal (:632-703) instead of ray samples
 constexpr uint32_t kFlagDepthTruncation = 4u;   // truncation + truncScale * depth (:815)
-constexpr uint32_t kFlagWalkShort = 32u;        // the table walk takes 4 entries per lane instead of 8 (option "walk_entries")
+constexpr uint32_t kFlagWalkShort = 32u;        // the table walk takes 4 entries per lane instead of 8 (set at creation)
 constexpr uint32_t kFlagWalkNt = 16u;           // the table walk's ptr loads are non-temporal (option "walk_nt")
 constexpr uint32_t kFlagBandRayDda = 64u;       // band allocation by the block DDA along the viewing ray (VH_BAND_RAY_DDA)
 constexpr uint32_t kFlagDebugNoProbe = 1u << 30;   // diagnostics builds only (VH_DEBUG_SKIP_ROLES): claim tiles return before probing

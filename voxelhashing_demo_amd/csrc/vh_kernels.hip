@@ -7,10 +7,10 @@
 //                      (VoxelUtils.cu:447-453, 328-334); key generation for the multi-GPU exchange
 //   vh_walk.hip        flattenIntoBuffer: the walk over the VoxelEntry array, wave-ballot
 //                      compaction of allocated in-frustum entries (flattenKernel, :719-749),
-//                      and the measured alternatives (wide chunks, occupancy index, ...)
+//                      and the walk over the bucket-occupancy bitmap that replaces it by default
 //   vh_integrate.hip   integrateDepthMap: one 8^3 block per workgroup pass, 16-byte-per-lane
 //                      voxel read-modify-write (integrateDepthMapKernel, :790-842)
-//   vh_frame.hip       the fused frame: {claim || walk} and {commit + integrate} in two launches
+//   vh_frame.hip       the fused frame: {claim || walk} and {commit + integrate} in two launches, or pipelined in one
 //   vh_shard.hip       the multi-camera frame on a bucket-range shard
 //   vh_raycast.hip     per-pixel march through the hash (stand-in for SDFRenderer::render,
 //                      SDFRenderer.cpp:210-255)

@@ -137,7 +137,7 @@ __device__ __forceinline__ void walk_process_tile(const FrameParams &fp, const D
     }
 }
 
-// Entries per lane of the frame's walk: 4 (kFlagWalkShort, set at creation; option "walk_entries" 4 | 8).
+// Entries per lane of the frame's walk: 4 (kFlagWalkShort, set at creation).
 // Twice the workgroups with half the loads each stream faster than 8 per lane once a workgroup costs
 // nothing before its first load (in-process, pipelined launch: C2 18.8 vs 19.4 us, C3 72.3 vs 75.4;
 // 3 per lane 18.8 / 75.1, 6 per lane 19.1 / 74.7, 2 per lane 19.5 / 79.6).  The multi-camera walk of the
