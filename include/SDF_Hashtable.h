@@ -15,6 +15,7 @@
 #define SDF_HASHTABLE_H
 
 #include <cstdint>
+#include <vector>
 
 #include "voxelhash.h"
 #include "voxelhash_dist.h"
@@ -80,6 +81,11 @@ public:
     /* SDFRenderer::drawToFrontAndBack (SDFRenderer.cpp:165-208): nearest front / farthest back face of the
      * allocated blocks' cubes per pixel, as two depth images (vh_render_blocks) */
     void renderBlocks(const float4x4 &pose, float *d_front, float *d_back, float zNear = 0.1f, float zFar = 5.0f);
+    /* The model as geometry (vh_extract_mesh: marching tetrahedra, world frame, wound towards free space): positions =
+     * 9 floats per triangle, normals (optional) one per vertex in the same layout.  Returns the triangle count.  Synchronises. */
+    uint64_t extractMesh(std::vector<float> &positions, std::vector<float> *normals = nullptr);
+    /* ... written as a binary little-endian PLY (three vertices per triangle, not welded); returns the triangle count */
+    uint64_t saveMeshPly(const char *path, bool withNormals = true);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

@@ -551,6 +551,42 @@ int vh_delete_blocks(vh_context *ctx, const int32_t *d_keys, int32_t n);
 int vh_garbage_collect(vh_context *ctx, float sdf_threshold);
 
 /* ------------------------------------------------------------------ */
+/* the model as geometry: triangle mesh of the TSDF's zero level        */
+/* ------------------------------------------------------------------ */
+/* Marching tetrahedra on the Kuhn split (six tetrahedra around the diagonal of every cell, the same split in every cell:
+ * no ambiguous cases, a closed 2-manifold wherever the volume is; DESIGN.md "mesh" has the full rule).  A voxel is valid
+ * iff its block is allocated (in this table / shard) and its weight > 0, inside iff sdf <= 0.  A cell -- voxel (x,y,z)
+ * and its +1 neighbours, owned by the block of (x,y,z) -- emits triangles iff all eight corners are valid.  A vertex
+ * lies on a cell edge, face diagonal or the cell diagonal between voxels A <= B: t = sA / (sA - sB), position
+ * (A + t on the axes where B = A + 1) * voxelSize, world frame, in both semantics; the arithmetic depends on the edge
+ * alone, so triangles that share an edge share the vertex bit for bit and welding is an exact `unique`.  Triangles are
+ * wound so that (v1 - v0) x (v2 - v0) points towards positive sdf (free space).  Zero-area triangles (a vertex on a
+ * corner) are not filtered.
+ *   region: the cells of the blocks block_lo <= key < block_hi per axis; NULL = the whole model.
+ *   d_positions: capacity_triangles * 9 floats (device), three vertices per triangle; may be NULL when the capacity is 0.
+ *   d_normals: NULL, or capacity_triangles * 9 floats: per vertex the TSDF gradients at A and B (the rule of
+ *     vh_raycast_normals, not normalised) blended as gA + t * (gB - gA), then normalised; world frame; (0,0,0) where an
+ *     end has no gradient.
+ *   triangles_out (host): the triangles the region holds, also when that exceeds the capacity -- then the first
+ *     `capacity_triangles` in output order are written and nothing beyond the buffers is touched (VH_OK).
+ *     capacity 0 with NULL buffers is the count-only call.
+ * Output order is reproducible: blocks in ascending entry index of the hash table, cells in ascending voxel index
+ * within the block, tetrahedra 0..5, triangles in table order -- the same table gives the same bytes.
+ * Runs on the context's stream behind every frame queued so far (a pending pipelined frame is launched first) and
+ * synchronises to return the count.  Works on shards (cells that need a block of another shard emit nothing) and on
+ * view tables (vh_import_view(s)).  Scratch is allocated at the first call and kept; frames are not affected. */
+typedef struct vh_mesh_region { int32_t block_lo[3], block_hi[3]; } vh_mesh_region; /* cells of blocks lo <= k < hi */
+int vh_extract_mesh(vh_context *ctx, const vh_mesh_region *region /* NULL: whole model */,
+                    uint64_t capacity_triangles,
+                    float *d_positions   /* capacity*9 floats, may be NULL when capacity is 0 */,
+                    float *d_normals     /* capacity*9 floats or NULL */,
+                    uint64_t *triangles_out /* host: triangles the region holds, even if > capacity */);
+/* The same with HOST output buffers (device buffers for the duration of the call, one copy back): for callers that have
+ * no HIP runtime of their own, like the C++ facade.  Not a hot path. */
+int vh_extract_mesh_host(vh_context *ctx, const vh_mesh_region *region, uint64_t capacity_triangles,
+                         float *h_positions, float *h_normals, uint64_t *triangles_out);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to

@@ -3,7 +3,8 @@
 through the C-ABI: uint16 depth -> vertex/normal maps (preProcess) -> pose from frame-to-model ICP
 against a raycast of the model (CameraTracking::Align; bypassed in the reference, Application.cpp:75)
 -> TSDF integration (SDF_Hashtable::integrate) -> periodic garbage collection.  Prints the time per
-stage and the drift against the true trajectory.   tools/pipeline_demo.py [frames]"""
+stage and the drift against the true trajectory; --mesh writes the fused model as a triangle mesh at the end.
+tools/pipeline_demo.py [frames] [--mesh out.ply]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,7 +13,12 @@ import voxelhashing_demo_amd as V
 from voxelhashing_demo_amd import synth, tracking
 
 W, H = 640, 480
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 60
+argv = sys.argv[1:]
+MESH = None
+if "--mesh" in argv:
+    MESH = argv[argv.index("--mesh") + 1]
+    del argv[argv.index("--mesh"):argv.index("--mesh") + 2]
+N = int(argv[0]) if argv else 60
 gt = synth.camera_loop(500)[200:200 + N]
 prims = synth.room_primitives()
 K = synth.K_matrix(W, H)
@@ -61,3 +67,12 @@ for name, t in stage.items():
     n = N - 1 if name in ("raycast_target", "align") else (N // 20 if name == "collect" else N)
     print(f"  {name:15s} {1e6 * t / max(1, n):8.1f} us per call (host-timed, synchronised)")
 print(f"  drift: max {1e3 * max(errs):.2f} mm, final {1e3 * errs[-1]:.2f} mm")
+if MESH:
+    from voxelhashing_demo_amd import mesh_io
+    with torch.cuda.stream(stream):
+        count = table.mesh_count()
+        t0 = time.perf_counter()
+        mv, mf, mn = table.extract_mesh(normals=True, weld=True)
+        dt = time.perf_counter() - t0
+    mesh_io.save_ply(MESH, mv, mf, mn)
+    print(f"mesh: triangles={count} vertices={len(mv)} ({1e3 * dt:.1f} ms with download and welding) -> {MESH}")

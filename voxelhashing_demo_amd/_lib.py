@@ -67,6 +67,11 @@ class KernelTimes(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MeshRegion(C.Structure):
+    """vh_mesh_region: the cells of the blocks block_lo <= key < block_hi."""
+    _fields_ = [("block_lo", C.c_int32 * 3), ("block_hi", C.c_int32 * 3)]
+
+
 class IcpSystem(C.Structure):
     _fields_ = [("JTJ", C.c_double * 36), ("JTr", C.c_double * 6), ("error", C.c_double), ("count", C.c_uint32)]
 
@@ -127,6 +132,8 @@ SIGNATURES = {
     "vh_write_packets_u16_batch": (C.c_int, [_vp, C.c_int32, _fp, C.POINTER(_vp), _fp, _vp, C.c_size_t]),
     "vh_delete_blocks": (C.c_int, [_vp, _vp, C.c_int32]),
     "vh_garbage_collect": (C.c_int, [_vp, _f]),
+    "vh_extract_mesh": (C.c_int, [_vp, C.POINTER(MeshRegion), C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "vh_extract_mesh_host": (C.c_int, [_vp, C.POINTER(MeshRegion), C.c_uint64, _fp, _fp, C.POINTER(C.c_uint64)]),
     "vh_export_views": (C.c_int, [_vp, _fp, C.c_int32, _f, _f, _vp, C.c_int32, _vp]),
     "vh_import_view": (C.c_int, [_vp, _vp, C.c_int32]),
     "vh_synchronize": (C.c_int, [_vp]),

@@ -113,6 +113,41 @@ void SDF_Hashtable::renderBlocks(const float4x4 &pose, float *d_front, float *d_
     check(vh_render_blocks(ctx_, pose.entries, zNear, zFar, d_front, d_back), "renderBlocks");
 }
 
+uint64_t SDF_Hashtable::extractMesh(std::vector<float> &positions, std::vector<float> *normals)
+{
+    uint64_t count = 0, got = 0;
+    check(vh_extract_mesh_host(ctx_, nullptr, 0, nullptr, nullptr, &count), "extractMesh");
+    positions.assign((size_t)count * 9, 0.0f);
+    if (normals) normals->assign((size_t)count * 9, 0.0f);
+    if (count)
+        check(vh_extract_mesh_host(ctx_, nullptr, count, positions.data(), normals ? normals->data() : nullptr, &got), "extractMesh");
+    return count;
+}
+
+uint64_t SDF_Hashtable::saveMeshPly(const char *path, bool withNormals)
+{
+    std::vector<float> pos, nrm;
+    const uint64_t count = extractMesh(pos, withNormals ? &nrm : nullptr);
+    FILE *f = std::fopen(path, "wb");
+    if (!f) { std::fprintf(stderr, "SDF_Hashtable: cannot write %s\n", path); std::exit(EXIT_FAILURE); }
+    std::fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n",
+                 (unsigned long long)(3 * count));
+    if (withNormals) std::fprintf(f, "property float nx\nproperty float ny\nproperty float nz\n");
+    std::fprintf(f, "element face %llu\nproperty list uchar int vertex_indices\nend_header\n", (unsigned long long)count);
+    for (uint64_t v = 0; v < 3 * count; ++v) {
+        std::fwrite(&pos[3 * v], sizeof(float), 3, f);
+        if (withNormals) std::fwrite(&nrm[3 * v], sizeof(float), 3, f);
+    }
+    for (uint64_t t = 0; t < count; ++t) {
+        const unsigned char three = 3;
+        const int32_t idx[3] = {(int32_t)(3 * t), (int32_t)(3 * t + 1), (int32_t)(3 * t + 2)};
+        std::fwrite(&three, 1, 1, f);
+        std::fwrite(idx, sizeof(int32_t), 3, f);
+    }
+    std::fclose(f);
+    return count;
+}
+
 void SDF_Hashtable::garbageCollect(float sdfThreshold)
 {
     check(vh_garbage_collect(ctx_, sdfThreshold), "garbageCollect");

@@ -213,6 +213,11 @@ struct vh_context {
     int blockParity = 0;                   // which counter word the next vh_render_blocks appends through
     const Voxel *viewBlocks = nullptr;     // import: the record buffer the view table's ptrs address
     int32_t viewCount = 0;                 // records of the last import (their buckets are listed in compactMask)
+    // vh_extract_mesh (vh_api_mesh.hip): scratch of the first call, kept
+    DevBuf<int4> meshItems;                // the listed blocks {x, y, z, ptr}, in entry order
+    DevBuf<uint32_t> meshCounts;           // per-slice entry counts, then per-block triangle counts (scanned in place)
+    DevBuf<unsigned long long> meshTotals; // the scans' tile totals, then {listed blocks, triangles}
+    int meshVariant = 0;                   // option "mesh_variant": 0 = 9^3 apron in LDS, 1 = corners straight from global memory
 };
 
 struct DeviceGuard {
@@ -557,6 +562,7 @@ static int ensure_candidates(vh_context *c, size_t need)
 #include "vh_api_frame.hip"
 #include "vh_api_shard.hip"
 #include "vh_api_model.hip"
+#include "vh_api_mesh.hip"
 #include "vh_api_dropin.hip"
 #include "vh_api_icp.hip"
 #include "vh_api_dist.hip"

@@ -67,6 +67,7 @@ class SDFHashtable:
         self.params = params if params is not None else default_params()
         self.width, self.height, self.semantics = width, height, semantics
         cfg = L.Config(self.params, width, height, semantics, device)
+        self._device = device
         h = C.c_void_p()
         if bucket_range is None:
             L.check(self._lib.vh_create(C.byref(cfg), C.byref(h)), "vh_create")
@@ -193,6 +194,54 @@ class SDFHashtable:
 
     def garbage_collect(self, sdf_threshold: float):
         L.check(self._lib.vh_garbage_collect(self._h, float(sdf_threshold)), "vh_garbage_collect")
+
+    # ---- the model as geometry (DESIGN.md "mesh") ----
+    @staticmethod
+    def _mesh_region(region):
+        if region is None:
+            return None
+        lo, hi = region
+        return C.byref(L.MeshRegion((C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in hi])))
+
+    def extract_mesh_into(self, capacity: int, positions, normals=None, region=None) -> int:
+        """vh_extract_mesh into caller-owned device buffers ([capacity, 3, 3] float32, or None with capacity 0);
+        returns the triangles the region holds, which may exceed `capacity`."""
+        n = C.c_uint64()
+        L.check(self._lib.vh_extract_mesh(self._h, self._mesh_region(region), int(capacity), _dev_ptr(positions),
+                                          _dev_ptr(normals), C.byref(n)), "vh_extract_mesh")
+        return int(n.value)
+
+    def mesh_count(self, region=None) -> int:
+        """Triangles of the zero level inside `region` = ((lo x, y, z), (hi x, y, z)) in blocks, None = the whole model."""
+        return self.extract_mesh_into(0, None, None, region)
+
+    def extract_mesh(self, region=None, normals: bool = False, weld: bool = False):
+        """The triangle mesh of the model (marching tetrahedra, world frame, wound towards free space), extracted on the GPU.
+        weld=False: triangles [T, 3, 3] float32 (and per-vertex normals [T, 3, 3] with normals=True).
+        weld=True: vertices [V, 3] float32 and faces [T, 3] int32 (shared vertices are bit-equal, so the welding is an exact
+        `unique` on the host), and per-vertex normals [V, 3] with normals=True.  Returns a tuple in that order."""
+        import torch
+        count = self.mesh_count(region)
+        with torch.cuda.device(self.device_index()):
+            pos = torch.empty((count, 3, 3), dtype=torch.float32, device="cuda")
+            nrm = torch.empty((count, 3, 3), dtype=torch.float32, device="cuda") if normals else None
+        if count:
+            got = self.extract_mesh_into(count, pos, nrm, region)
+            if got != count:
+                raise L.VoxelHashError(f"the model changed between the count ({count}) and the extraction ({got})")
+        tris = pos.cpu().numpy()
+        nn = nrm.cpu().numpy() if normals else None
+        if not weld:
+            return (tris, nn) if normals else tris
+        from .mesh_io import weld_triangles
+        verts, faces, first = weld_triangles(tris)
+        return (verts, faces, nn.reshape(-1, 3)[first]) if normals else (verts, faces)
+
+    def device_index(self) -> int:
+        """Ordinal of the device the context lives on."""
+        import torch
+        dev = getattr(self, "_device", -1)
+        return torch.cuda.current_device() if dev is None or dev < 0 else dev
 
     # ---- raycast over shards (DESIGN.md section 6 "raycast") ----
     VIEW_RECORD_BYTES = 4112
