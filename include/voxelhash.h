@@ -570,6 +570,10 @@ int vh_garbage_collect(vh_context *ctx, float sdf_threshold);
  *   triangles_out (host): the triangles the region holds, also when that exceeds the capacity -- then the first
  *     `capacity_triangles` in output order are written and nothing beyond the buffers is touched (VH_OK).
  *     capacity 0 with NULL buffers is the count-only call.
+ * Key domain: |key| < 2^28 on every axis (the voxel coordinate 8 * key + 0..7 must fit an int32; it is computed in wrapping
+ * 32-bit arithmetic, so a key outside the domain gives unspecified positions).  Negative keys are fine.  From |8 * key| >= 2^24
+ * on, the coordinate is rounded to the nearest float32 (the same bits as the specification, but vertices of a block coincide).
+ * Region bounds may be any int32.
  * Output order is reproducible: blocks in ascending entry index of the hash table, cells in ascending voxel index
  * within the block, tetrahedra 0..5, triangles in table order -- the same table gives the same bytes.
  * Runs on the context's stream behind every frame queued so far (a pending pipelined frame is launched first) and
