@@ -86,6 +86,12 @@ public:
     uint64_t extractMesh(std::vector<float> &positions, std::vector<float> *normals = nullptr);
     /* ... written as a binary little-endian PLY (three vertices per triangle, not welded); returns the triangle count */
     uint64_t saveMeshPly(const char *path, bool withNormals = true);
+    /* The indexed form (vh_extract_mesh_indexed: one vertex per cell edge, never welded by position): vertices = 3 floats
+     * per vertex, indices = 3 per triangle in extractMesh's order, normals (optional) one per vertex.  Returns the
+     * triangle count.  Synchronises. */
+    uint64_t extractMeshIndexed(std::vector<float> &vertices, std::vector<uint32_t> &indices, std::vector<float> *normals = nullptr);
+    /* ... written as a binary little-endian PLY with shared vertices; returns the triangle count */
+    uint64_t saveMeshPlyIndexed(const char *path, bool withNormals = true);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

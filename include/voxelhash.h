@@ -590,6 +590,44 @@ int vh_extract_mesh(vh_context *ctx, const vh_mesh_region *region /* NULL: whole
 int vh_extract_mesh_host(vh_context *ctx, const vh_mesh_region *region, uint64_t capacity_triangles,
                          float *h_positions, float *h_normals, uint64_t *triangles_out);
 
+/* The same surface in INDEXED form: one vertex buffer, three uint32 indices per triangle.  Everything vh_extract_mesh
+ * specifies stays (which cells emit, the triangles, their order, the winding, the arithmetic of a position and a normal).
+ *   A vertex is identified by its EDGE (A, d): A the global voxel coordinate of the lower end (the end t is measured
+ *     from), d = 1..7 the bit set of axes (x = 1, y = 2, z = 4) on which the upper end is A + 1: three axis edges, three
+ *     face diagonals and the cell diagonal are anchored at every voxel.  Two edges whose positions have equal bits (t = 0
+ *     or 1 at an sdf of +-0, float32 rounding from |8 * key| >= 2^24 on) stay two vertices: sheets that only touch are
+ *     not glued, which a weld by position would do.  Welded by edge the mesh is a closed 2-manifold wherever the volume
+ *     is: no directed edge (i, j) occurs twice.
+ *   Vertex (A, d) exists iff an emitted triangle of the region uses it: both ends valid with different inside flags, and
+ *     one of the one, two or four cells that contain the edge (corner 0 at A - o, o a bit set disjoint from d) has eight
+ *     valid corners and lies in a block of the region.
+ *   Vertex order: ascending (entry index in the hash table of the block that holds voxel A, voxel index of A in that
+ *     block, d).  A may lie in a +neighbour of the block that owns the cell, also one outside the region: the blocks
+ *     that can hold vertices are the allocated ones with block_lo <= key < block_hi + 1 per axis (saturating).
+ *   d_indices: three per triangle, triangles in the order of vh_extract_mesh.  d_vertices[d_indices[i]] has the bits
+ *     vh_extract_mesh writes for corner i of the same table and region, and so has d_vertex_normals (one normal per
+ *     vertex, the same rule: it depends on the edge alone).
+ *   vertices_out, triangles_out (host): what the region holds, also when that exceeds a capacity -- then the first
+ *     capacity_vertices vertices and the first capacity_triangles triangles in order are written and nothing beyond the
+ *     buffers is touched (VH_OK).  Indices in a clipped index buffer may name vertices at or beyond capacity_vertices.
+ *     Both capacities 0 with NULL buffers is the count-only call.
+ *   A region with more than 2^32 - 1 vertices cannot be indexed: both counts are reported, nothing is written and the
+ *     call returns VH_ERR_INVALID_ARGUMENT (extract by regions instead).
+ * Key domain, stream order, the one synchronisation, shards (a cell that needs a block of another shard emits nothing,
+ * and so do the vertices only such cells would use) and view tables as for vh_extract_mesh.  Scratch of the indexed call
+ * (2 KB and a few words per block the table can hold) is allocated at its first use and kept; a context that never
+ * calls it allocates nothing for it. */
+int vh_extract_mesh_indexed(vh_context *ctx, const vh_mesh_region *region /* NULL: whole model */,
+                            uint64_t capacity_vertices, uint64_t capacity_triangles,
+                            float *d_vertices        /* capacity_vertices * 3 floats, may be NULL when that is 0 */,
+                            float *d_vertex_normals  /* capacity_vertices * 3 floats or NULL */,
+                            uint32_t *d_indices      /* capacity_triangles * 3, may be NULL when that is 0 */,
+                            uint64_t *vertices_out, uint64_t *triangles_out /* host; what the region holds */);
+/* The same with HOST output buffers, as vh_extract_mesh_host: for the C++ facade.  Not a hot path. */
+int vh_extract_mesh_indexed_host(vh_context *ctx, const vh_mesh_region *region, uint64_t capacity_vertices,
+                                 uint64_t capacity_triangles, float *h_vertices, float *h_vertex_normals,
+                                 uint32_t *h_indices, uint64_t *vertices_out, uint64_t *triangles_out);
+
 /* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */

@@ -3,8 +3,9 @@
 through the C-ABI: uint16 depth -> vertex/normal maps (preProcess) -> pose from frame-to-model ICP
 against a raycast of the model (CameraTracking::Align; bypassed in the reference, Application.cpp:75)
 -> TSDF integration (SDF_Hashtable::integrate) -> periodic garbage collection.  Prints the time per
-stage and the drift against the true trajectory; --mesh writes the fused model as a triangle mesh at the end.
-tools/pipeline_demo.py [frames] [--mesh out.ply]"""
+stage and the drift against the true trajectory; --mesh writes the fused model as a triangle mesh at the end
+(welded by position on the host), --mesh-indexed the indexed mesh the GPU makes (one vertex per cell edge).
+tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -14,7 +15,10 @@ from voxelhashing_demo_amd import synth, tracking
 
 W, H = 640, 480
 argv = sys.argv[1:]
-MESH = None
+MESH = MESH_INDEXED = None
+if "--mesh-indexed" in argv:
+    MESH_INDEXED = argv[argv.index("--mesh-indexed") + 1]
+    del argv[argv.index("--mesh-indexed"):argv.index("--mesh-indexed") + 2]
 if "--mesh" in argv:
     MESH = argv[argv.index("--mesh") + 1]
     del argv[argv.index("--mesh"):argv.index("--mesh") + 2]
@@ -76,3 +80,11 @@ if MESH:
         dt = time.perf_counter() - t0
     mesh_io.save_ply(MESH, mv, mf, mn)
     print(f"mesh: triangles={count} vertices={len(mv)} ({1e3 * dt:.1f} ms with download and welding) -> {MESH}")
+if MESH_INDEXED:
+    from voxelhashing_demo_amd import mesh_io
+    with torch.cuda.stream(stream):
+        t0 = time.perf_counter()
+        mv, mf, mn = table.extract_mesh_indexed(normals=True)
+        dt = time.perf_counter() - t0
+    mesh_io.save_ply(MESH_INDEXED, mv, mf, mn)
+    print(f"mesh indexed: triangles={len(mf)} vertices={len(mv)} ({1e3 * dt:.1f} ms with download) -> {MESH_INDEXED}")

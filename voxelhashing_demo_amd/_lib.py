@@ -134,6 +134,10 @@ SIGNATURES = {
     "vh_garbage_collect": (C.c_int, [_vp, _f]),
     "vh_extract_mesh": (C.c_int, [_vp, C.POINTER(MeshRegion), C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
     "vh_extract_mesh_host": (C.c_int, [_vp, C.POINTER(MeshRegion), C.c_uint64, _fp, _fp, C.POINTER(C.c_uint64)]),
+    "vh_extract_mesh_indexed": (C.c_int, [_vp, C.POINTER(MeshRegion), C.c_uint64, C.c_uint64, _vp, _vp, _vp,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vh_extract_mesh_indexed_host": (C.c_int, [_vp, C.POINTER(MeshRegion), C.c_uint64, C.c_uint64, _fp, _fp,
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vh_export_views": (C.c_int, [_vp, _fp, C.c_int32, _f, _f, _vp, C.c_int32, _vp]),
     "vh_import_view": (C.c_int, [_vp, _vp, C.c_int32]),
     "vh_synchronize": (C.c_int, [_vp]),

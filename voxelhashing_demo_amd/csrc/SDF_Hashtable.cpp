@@ -148,6 +148,46 @@ uint64_t SDF_Hashtable::saveMeshPly(const char *path, bool withNormals)
     return count;
 }
 
+uint64_t SDF_Hashtable::extractMeshIndexed(std::vector<float> &vertices, std::vector<uint32_t> &indices, std::vector<float> *normals)
+{
+    uint64_t nv = 0, nt = 0, gv = 0, gt = 0;
+    check(vh_extract_mesh_indexed_host(ctx_, nullptr, 0, 0, nullptr, nullptr, nullptr, &nv, &nt), "extractMeshIndexed");
+    vertices.assign((size_t)nv * 3, 0.0f);
+    indices.assign((size_t)nt * 3, 0u);
+    if (normals) normals->assign((size_t)nv * 3, 0.0f);
+    if (nv || nt)
+        check(vh_extract_mesh_indexed_host(ctx_, nullptr, nv, nt, vertices.data(), normals ? normals->data() : nullptr, indices.data(),
+                                           &gv, &gt), "extractMeshIndexed");
+    return nt;
+}
+
+uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
+{
+    std::vector<float> pos, nrm;
+    std::vector<uint32_t> idx;
+    const uint64_t count = extractMeshIndexed(pos, idx, withNormals ? &nrm : nullptr);
+    const uint64_t nv = pos.size() / 3;
+    if (nv > (uint64_t)INT32_MAX) { std::fprintf(stderr, "SDF_Hashtable: %llu vertices do not fit a PLY int index\n", (unsigned long long)nv); std::exit(EXIT_FAILURE); }
+    FILE *f = std::fopen(path, "wb");
+    if (!f) { std::fprintf(stderr, "SDF_Hashtable: cannot write %s\n", path); std::exit(EXIT_FAILURE); }
+    std::fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n",
+                 (unsigned long long)nv);
+    if (withNormals) std::fprintf(f, "property float nx\nproperty float ny\nproperty float nz\n");
+    std::fprintf(f, "element face %llu\nproperty list uchar int vertex_indices\nend_header\n", (unsigned long long)count);
+    for (uint64_t v = 0; v < nv; ++v) {
+        std::fwrite(&pos[3 * v], sizeof(float), 3, f);
+        if (withNormals) std::fwrite(&nrm[3 * v], sizeof(float), 3, f);
+    }
+    for (uint64_t t = 0; t < count; ++t) {
+        const unsigned char three = 3;
+        const int32_t tri[3] = {(int32_t)idx[3 * t], (int32_t)idx[3 * t + 1], (int32_t)idx[3 * t + 2]};
+        std::fwrite(&three, 1, 1, f);
+        std::fwrite(tri, sizeof(int32_t), 3, f);
+    }
+    std::fclose(f);
+    return count;
+}
+
 void SDF_Hashtable::garbageCollect(float sdfThreshold)
 {
     check(vh_garbage_collect(ctx_, sdfThreshold), "garbageCollect");

@@ -218,6 +218,9 @@ struct vh_context {
     DevBuf<uint32_t> meshCounts;           // per-slice entry counts, then per-block triangle counts (scanned in place)
     DevBuf<unsigned long long> meshTotals; // the scans' tile totals, then {listed blocks, triangles}
     int meshVariant = 0;                   // option "mesh_variant": 0 = 9^3 apron in LDS, 1 = corners straight from global memory
+    // vh_extract_mesh_indexed: scratch of its first call, kept
+    DevBuf<uint32_t> meshWords;            // per listed block 512 words {vertex prefix << 7 | edge mask}, then the per-block vertex counts, then listPos[ptr >> 9]
+    DevBuf<unsigned long long> meshVertexTotals;   // the vertex scan's tile totals, then {listed blocks, vertices, triangles}
 };
 
 struct DeviceGuard {

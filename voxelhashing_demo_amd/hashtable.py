@@ -219,7 +219,10 @@ class SDFHashtable:
         """The triangle mesh of the model (marching tetrahedra, world frame, wound towards free space), extracted on the GPU.
         weld=False: triangles [T, 3, 3] float32 (and per-vertex normals [T, 3, 3] with normals=True).
         weld=True: vertices [V, 3] float32 and faces [T, 3] int32 (shared vertices are bit-equal, so the welding is an exact
-        `unique` on the host), and per-vertex normals [V, 3] with normals=True.  Returns a tuple in that order."""
+        `unique` on the host), and per-vertex normals [V, 3] with normals=True.  Returns a tuple in that order.
+        The weld is by position bits, sorted on the host.  extract_mesh_indexed() gives the indexed form straight from the
+        GPU, without the sort, and identifies a vertex by its cell edge: edges whose positions coincide (an sdf of +-0, keys
+        beyond float32's integers) stay separate vertices there and are merged here, and the vertex order differs."""
         import torch
         count = self.mesh_count(region)
         with torch.cuda.device(self.device_index()):
@@ -236,6 +239,40 @@ class SDFHashtable:
         from .mesh_io import weld_triangles
         verts, faces, first = weld_triangles(tris)
         return (verts, faces, nn.reshape(-1, 3)[first]) if normals else (verts, faces)
+
+    def extract_mesh_indexed_into(self, capacity_vertices: int, capacity_triangles: int, vertices, indices, normals=None,
+                                  region=None):
+        """vh_extract_mesh_indexed into caller-owned device buffers (vertices, normals: [capacity_vertices, 3] float32;
+        indices: [capacity_triangles, 3] int32 or uint32; None with a capacity of 0).  Returns (V, T), what the region holds,
+        which may exceed the capacities."""
+        nv, nt = C.c_uint64(), C.c_uint64()
+        L.check(self._lib.vh_extract_mesh_indexed(self._h, self._mesh_region(region), int(capacity_vertices),
+                                                  int(capacity_triangles), _dev_ptr(vertices), _dev_ptr(normals),
+                                                  _dev_ptr(indices), C.byref(nv), C.byref(nt)), "vh_extract_mesh_indexed")
+        return int(nv.value), int(nt.value)
+
+    def mesh_counts(self, region=None):
+        """(vertices, triangles) of the indexed mesh inside `region`, None = the whole model."""
+        return self.extract_mesh_indexed_into(0, 0, None, None, None, region)
+
+    def extract_mesh_indexed(self, region=None, normals: bool = False):
+        """The mesh of extract_mesh() in indexed form, made on the GPU: (vertices [V, 3] float32, faces [T, 3] int32) and
+        per-vertex normals [V, 3] with normals=True.  One vertex per cell edge with a sign change (never merged by position);
+        vertices[faces] has the bits of extract_mesh(), triangle for triangle."""
+        import torch
+        nv, nt = self.mesh_counts(region)
+        if nv > 2**31 - 1:
+            raise L.VoxelHashError(f"{nv} vertices do not fit int32 faces: extract by regions")
+        with torch.cuda.device(self.device_index()):
+            pos = torch.empty((nv, 3), dtype=torch.float32, device="cuda")
+            idx = torch.empty((nt, 3), dtype=torch.int32, device="cuda")
+            nrm = torch.empty((nv, 3), dtype=torch.float32, device="cuda") if normals else None
+        if nv or nt:
+            got = self.extract_mesh_indexed_into(nv, nt, pos, idx, nrm, region)
+            if got != (nv, nt):
+                raise L.VoxelHashError(f"the model changed between the count ({nv}, {nt}) and the extraction {got}")
+        out = (pos.cpu().numpy(), idx.cpu().numpy())
+        return out + (nrm.cpu().numpy(),) if normals else out
 
     def device_index(self) -> int:
         """Ordinal of the device the context lives on."""
