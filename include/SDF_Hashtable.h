@@ -92,6 +92,11 @@ public:
     uint64_t extractMeshIndexed(std::vector<float> &vertices, std::vector<uint32_t> &indices, std::vector<float> *normals = nullptr);
     /* ... written as a binary little-endian PLY with shared vertices; returns the triangle count */
     uint64_t saveMeshPlyIndexed(const char *path, bool withNormals = true);
+    /* The model as a distance field (vh_sample_sdf, through host buffers): points = 3 floats per point, world metres;
+     * mode = VH_SAMPLE_NEAREST or VH_SAMPLE_TRILINEAR; sdf = one float per point, NaN where there is no valid sample;
+     * weight (optional) one per point, gradient (optional) three per point, per world metre.  Synchronises. */
+    void sampleSdf(const std::vector<float> &points, int mode, std::vector<float> &sdf, std::vector<float> *weight = nullptr,
+                   std::vector<float> *gradient = nullptr);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

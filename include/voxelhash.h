@@ -629,6 +629,48 @@ int vh_extract_mesh_indexed_host(vh_context *ctx, const vh_mesh_region *region, 
                                  uint32_t *h_indices, uint64_t *vertices_out, uint64_t *triangles_out);
 
 /* ------------------------------------------------------------------ */
+/* the model as a distance field                                       */
+/* ------------------------------------------------------------------ */
+/* Signed distance, weight and gradient of the fused TSDF at world points, and dense boxes of the voxel lattice
+ * (tests/sample_ref.py is the rule in executable form).  IEEE fp32, unfused multiply and add, in the order
+ * written here: the same model gives the same bits.
+ *   A voxel with integer coordinate g sits at g * voxelSize in the world frame (the mesh's convention, both semantics); it is
+ *   valid iff its block is allocated in this table / shard, its weight > 0 and its sdf is not NaN (the mesh's rule).
+ *   A point p has u = p / voxelSize per axis; a point with an axis failing |u| < 2^30 (NaN and +-inf among them) has no sample.
+ *   No sample: sdf NaN, weight 0, gradient (NaN, NaN, NaN).
+ *   VH_SAMPLE_NEAREST: the voxel (int)(u + copysign(0.5, u)), truncating (world2Voxel's rule); sdf and weight are its own
+ *     when it is valid.  Gradient: the rule of the mesh normals at that voxel, per axis (s+ - s-) * 0.5 where both neighbours
+ *     are valid, s+ - here or here - s- where one is, each divided by voxelSize; an axis with neither makes the whole
+ *     gradient NaN.
+ *   VH_SAMPLE_TRILINEAR: f = floor(u), i = (int)f, t = u - f; corner c (bit 0 = x, 1 = y, 2 = z) is voxel i + c.  A sample
+ *     iff all eight corners are valid (also for a point exactly on the lattice).  With lerp(a, b, t) = a + t * (b - a):
+ *       sdf = lerp(lerp(lerp(s0,s1,tx), lerp(s2,s3,tx), ty), lerp(lerp(s4,s5,tx), lerp(s6,s7,tx), ty), tz),
+ *       weight the same on the eight weights,
+ *       gx = lerp(lerp(s1-s0, s3-s2, ty), lerp(s5-s4, s7-s6, ty), tz) / voxelSize, gy and gz alike on their axes.
+ *     A stored +-inf goes through the arithmetic as IEEE has it.
+ * Both device calls only enqueue work on the context's stream, behind every frame queued so far (a pending pipelined frame
+ * is launched first); they read nothing back, do not synchronise, allocate nothing and change nothing in the model.  They
+ * work on shards (a block of another shard is absent: a sample that needs one is NaN) and on view tables, with or without
+ * the overflow list.  n == 0 or a zero entry of dims: VH_OK, nothing is launched.  VH_ERR_INVALID_ARGUMENT: n > 2^31 - 1,
+ * an unknown mode, NULL d_points or d_sdf with n > 0, a negative entry of dims, lo + dims beyond int32 on an axis. */
+#define VH_SAMPLE_NEAREST   0
+#define VH_SAMPLE_TRILINEAR 1
+int vh_sample_sdf(vh_context *ctx, int32_t mode, uint64_t n,
+                  const float *d_points   /* n*3 floats, world metres, packed xyz: the layout of d_vertices of vh_extract_mesh_indexed */,
+                  float *d_sdf            /* n floats; NaN = no valid sample */,
+                  float *d_weight         /* n floats or NULL */,
+                  float *d_gradient       /* n*3 floats or NULL: d sdf / d world metres */);
+/* The same with HOST buffers (device buffers for the duration of the call, one copy each way; synchronises): for the C++
+ * facade, as vh_extract_mesh_host.  Not a hot path. */
+int vh_sample_sdf_host(vh_context *ctx, int32_t mode, uint64_t n, const float *h_points, float *h_sdf, float *h_weight,
+                       float *h_gradient);
+/* The voxels lo <= g < lo + dims as dense arrays: element (k * dims[1] + j) * dims[0] + i is voxel lo + (i, j, k); the stored
+ * sdf where the voxel is valid, else NaN; the stored weight where valid, else 0. */
+int vh_sample_lattice(vh_context *ctx, const int32_t lo[3], const int32_t dims[3],
+                      float *d_sdf        /* dims[0]*dims[1]*dims[2] floats, x fastest */,
+                      float *d_weight     /* the same size or NULL */);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to

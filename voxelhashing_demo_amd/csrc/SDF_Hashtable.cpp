@@ -161,6 +161,17 @@ uint64_t SDF_Hashtable::extractMeshIndexed(std::vector<float> &vertices, std::ve
     return nt;
 }
 
+void SDF_Hashtable::sampleSdf(const std::vector<float> &points, int mode, std::vector<float> &sdf, std::vector<float> *weight,
+                              std::vector<float> *gradient)
+{
+    const uint64_t n = points.size() / 3;
+    sdf.assign((size_t)n, 0.0f);
+    if (weight) weight->assign((size_t)n, 0.0f);
+    if (gradient) gradient->assign((size_t)n * 3, 0.0f);
+    check(vh_sample_sdf_host(ctx_, mode, n, points.data(), sdf.data(), weight ? weight->data() : nullptr,
+                             gradient ? gradient->data() : nullptr), "sampleSdf");
+}
+
 uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
 {
     std::vector<float> pos, nrm;

@@ -20,6 +20,8 @@
 //   vh_gc.hip          block deletion / garbage collection (deleteVoxelEntry :544-604 done correctly)
 //   vh_mesh.hip        iso-surface extraction: ordered block list, marching tetrahedra per block behind a 9^3 apron in
 //                      LDS, count -> scan -> emit (no counterpart in the reference)
+//   vh_sample.hip      the model as a distance field: sdf / weight / gradient at world points (one point per lane),
+//                      dense boxes of the voxel lattice (one workgroup pass per brick; no counterpart in the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -42,3 +44,4 @@
 #include "vh_preprocess.hip"
 #include "vh_icp.hip"
 #include "vh_mesh.hip"
+#include "vh_sample.hip"

@@ -274,6 +274,44 @@ class SDFHashtable:
         out = (pos.cpu().numpy(), idx.cpu().numpy())
         return out + (nrm.cpu().numpy(),) if normals else out
 
+    # ---- the model as a distance field ----
+    def sample_sdf_into(self, points, sdf, weight=None, gradient=None, mode: int = L.SAMPLE_TRILINEAR, n: int = None):
+        """vh_sample_sdf into caller-owned device buffers: points [n, 3] float32 (world metres), sdf [n], weight [n] or None,
+        gradient [n, 3] or None.  Asynchronous on the context's stream."""
+        n = int(points.shape[0]) if n is None else int(n)
+        L.check(self._lib.vh_sample_sdf(self._h, int(mode), n, _dev_ptr(points), _dev_ptr(sdf), _dev_ptr(weight),
+                                        _dev_ptr(gradient)), "vh_sample_sdf")
+        return sdf
+
+    def sample_sdf(self, points, mode: int = L.SAMPLE_TRILINEAR, weight: bool = False, gradient: bool = False):
+        """The TSDF at world points [n, 3] (float32 CUDA tensor): sdf [n] (NaN where there is no valid sample), then
+        weight [n] and gradient [n, 3] (per world metre) when asked for, as CUDA tensors; a tuple when more than one."""
+        import torch
+        n = int(points.shape[0])
+        sdf = torch.empty((n,), dtype=torch.float32, device=points.device)
+        w = torch.empty((n,), dtype=torch.float32, device=points.device) if weight else None
+        g = torch.empty((n, 3), dtype=torch.float32, device=points.device) if gradient else None
+        self.sample_sdf_into(points, sdf, w, g, mode)
+        out = (sdf,) + ((w,) if weight else ()) + ((g,) if gradient else ())
+        return out if len(out) > 1 else sdf
+
+    def sample_lattice_into(self, lo, dims, sdf, weight=None):
+        """vh_sample_lattice into caller-owned device buffers of dims[0] * dims[1] * dims[2] floats, x fastest."""
+        lo3, d3 = (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in dims])
+        L.check(self._lib.vh_sample_lattice(self._h, lo3, d3, _dev_ptr(sdf), _dev_ptr(weight)), "vh_sample_lattice")
+        return sdf
+
+    def sample_lattice(self, lo, dims, weight: bool = False):
+        """The voxels lo <= g < lo + dims (global voxel coordinates, x, y, z) as a CUDA tensor [dims[2], dims[1], dims[0]]:
+        the stored sdf, NaN where the voxel is not valid; with weight=True also the weights (0 where not valid)."""
+        import torch
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        with torch.cuda.device(self.device_index()):
+            sdf = torch.empty(shape, dtype=torch.float32, device="cuda")
+            w = torch.empty(shape, dtype=torch.float32, device="cuda") if weight else None
+        self.sample_lattice_into(lo, dims, sdf, w)
+        return (sdf, w) if weight else sdf
+
     def device_index(self) -> int:
         """Ordinal of the device the context lives on."""
         import torch
