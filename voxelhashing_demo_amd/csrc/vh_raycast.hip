@@ -560,7 +560,11 @@ __device__ __forceinline__ DdaHit dda_lane_walk(const FrameParams &fp, const Dev
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {
                         const int nearC = (gk[a] << 3) + (ax[a].s > 0 ? 0 : 7), farC = (gk[a] << 3) + (ax[a].s > 0 ? 7 : 0);
-                        cc[a] = (a == eX2) ? nearC : (ax[a].invE == 0.0f ? c[a] : dda_advance(ax[a], prio[a], nearC, farC, eT2, pX));
+                        // never behind the ray's first voxel: the start floor(G + E t) may already lie past a crossing whose time
+                        // ties with the entry event and follows it in the merge order (the cooperative form: startIn)
+                        // (c is this function's argument, the ray's first voxel behind the front end -- not the running c0..c2)
+                        const int from = ax[a].s > 0 ? max(nearC, c[a]) : min(nearC, c[a]);
+                        cc[a] = (a == eX2) ? nearC : (ax[a].invE == 0.0f ? c[a] : dda_advance(ax[a], prio[a], from, farC, eT2, pX));
                     }
                     c0 = cc[0]; c1 = cc[1]; c2 = cc[2];
                 }
