@@ -97,6 +97,13 @@ public:
      * weight (optional) one per point, gradient (optional) three per point, per world metre.  Synchronises. */
     void sampleSdf(const std::vector<float> &points, int mode, std::vector<float> &sdf, std::vector<float> *weight = nullptr,
                    std::vector<float> *gradient = nullptr);
+    /* Where rays meet the surface (vh_cast_rays, through host buffers): rays = 8 floats per ray (origin, t_min, direction, t_max,
+     * the layout of vh_ray); depthPlane = four floats (one plane places the samples of all rays: row 2 of a pose's inverse gives
+     * the raycast's depths) or nullptr (along each ray); t = one float per ray, NaN where there is no hit; normals (optional)
+     * three per ray, world frame; voxels (optional) four per ray: the hit voxel and the status (1 hit, 0 miss, -1 refused).
+     * Synchronises. */
+    void castRays(const std::vector<float> &rays, const float *depthPlane, std::vector<float> &t, std::vector<float> *normals = nullptr,
+                  std::vector<int32_t> *voxels = nullptr);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

@@ -671,6 +671,53 @@ int vh_sample_lattice(vh_context *ctx, const int32_t lo[3], const int32_t dims[3
                       float *d_weight     /* the same size or NULL */);
 
 /* ------------------------------------------------------------------ */
+/* the model met by rays                                               */
+/* ------------------------------------------------------------------ */
+/* Where does this ray meet the surface: the DDA of vh_raycast with the camera taken out, for any batch of rays (DESIGN.md
+ * 4.10; tests/rays_ref.py is the rule in executable form).  IEEE fp32, every multiply and add rounded on its own, in the
+ * order written here: the same model and rays give the same bits.
+ *   A ray is O + t * D for t_min <= t, crossings taken while t < t_max; D need not be normalised.  Per axis a:
+ *     G_a = O_a / voxelSize + 0.5, E_a = D_a / voxelSize; the axis is active iff |E_a| > 1e-20, steps by s_a = +1 iff E_a > 0,
+ *     else -1; Gs_a = G_a - 1 for an axis that steps up, G_a otherwise.  The first voxel is floor(G + E * t_min).  The
+ *     crossing out of integer coordinate c happens at t_a(c) = ((float)c - Gs_a) * (1 / E_a), never for an inactive axis.  The
+ *     walk takes, again and again, the first pending crossing in the order (t, priority y < z < x); a crossing with
+ *     t >= t_max is not taken and ends the ray.  With O = a pose's translation and D_a = (T[a,0] * dx + T[a,1] * dy) + T[a,2]
+ *     these are the rays of vh_raycast, bit for bit.
+ *   Samples: a visited voxel (cx, cy, cz) of an allocated block with weight > 0, at parameter
+ *     t(c) = ((w0 * cx + w1 * cy) + w2 * cz) + w3.  With depth_plane = P one plane serves all rays:
+ *     w = (P0 * voxelSize, P1 * voxelSize, P2 * voxelSize, P3); row 2 of a pose's inverse makes t the camera depth, and the
+ *     results are then the bits of vh_raycast for the same rays.  With depth_plane = NULL the sample sits at the projection
+ *     of the voxel centre onto its own ray: dd = (Dx * Dx + Dy * Dy) + Dz * Dz, k = 1 / dd, w_a = (D_a * k) * voxelSize,
+ *     w3 = -(((Ox * Dx + Oy * Dy) + Oz * Dz) * k).
+ *   Hit: the first pair of consecutive visited voxels that are both samples with sdf_prev > 0 >= sdf_cur;
+ *     t = t_prev + ((t_cur - t_prev) * sdf_prev) / (sdf_prev - sdf_cur).
+ *   d_t: the hit's t, NaN where there is none.  d_voxels: {x, y, z, 1} of the pair's second voxel for a hit, {0, 0, 0, 0}
+ *     for a miss (the status word tells a miss from a hit whose arithmetic gives NaN, stored +-inf for instance).
+ *     d_normals: the gradient rule of vh_raycast_normals at that voxel, divided by its length when that is > 0 and every
+ *     axis has a neighbour, NOT rotated (world frame, towards positive sdf); zeros otherwise.
+ *   A refused ray has status -1, t = NaN, normal zeros and costs no walk.  Refused: a ray with a float that is not finite;
+ *     one for which t_max > t_min does not hold; dd == 0; one whose step bound
+ *     16 + sum_a (1.01 * (t_max - t_min) * |D_a| / voxelSize + 2) is not < 2^22 (the bound is also the ray's hang-guard
+ *     budget); one with |G_a| + (|t_max| + |t_min|) * |D_a| / voxelSize not < 2^23 on some axis.  The last two are the
+ *     bounds vh_raycast applies to a view, evaluated per ray on the device in double.
+ * The device call only enqueues work on the context's stream, behind every frame queued so far (a pending pipelined frame
+ * is launched first); it reads nothing back, does not synchronise, allocates nothing and changes nothing in the model.  It
+ * works on shards (a block of another shard is absent) and on view tables, with or without the overflow list.  n == 0:
+ * VH_OK, nothing is launched.  VH_ERR_INVALID_ARGUMENT: a null context, n > 2^31 - 1, NULL d_rays or d_t with n > 0, d_rays
+ * not 16-byte aligned, an entry of depth_plane that is not finite. */
+typedef struct vh_ray { float origin[3]; float t_min; float dir[3]; float t_max; } vh_ray;   /* 32 bytes */
+int vh_cast_rays(vh_context *ctx, uint64_t n,
+                 const vh_ray *d_rays            /* n rays, device, 16-byte aligned */,
+                 const float depth_plane[4]      /* host; NULL: samples are placed along each ray */,
+                 float *d_t                      /* n floats: ray parameter of the hit, NaN = none */,
+                 float *d_normals                /* n*3 floats or NULL: world-frame normal of the hit, zeros otherwise */,
+                 int32_t *d_voxels               /* n*4 int32 or NULL: hit voxel x, y, z and status */);
+/* The same with HOST buffers (device buffers for the duration of the call, one copy each way; synchronises): for the C++
+ * facade, as vh_sample_sdf_host.  Not a hot path. */
+int vh_cast_rays_host(vh_context *ctx, uint64_t n, const vh_ray *h_rays, const float depth_plane[4], float *h_t,
+                      float *h_normals, int32_t *h_voxels);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to

@@ -19,6 +19,7 @@ SEM_PINHOLE = 1
 BUF_HASH_TABLE, BUF_COMPACT, BUF_SDF_BLOCKS, BUF_HEAP = 0, 1, 2, 3
 FREE_BLOCK = -1
 SAMPLE_NEAREST, SAMPLE_TRILINEAR = 0, 1
+RAY_HIT, RAY_MISS, RAY_REFUSED = 1, 0, -1          # the status word of vh_cast_rays' d_voxels
 
 
 class HashTableParams(C.Structure):
@@ -142,6 +143,8 @@ SIGNATURES = {
     "vh_sample_sdf": (C.c_int, [_vp, _i32, C.c_uint64, _vp, _vp, _vp, _vp]),
     "vh_sample_sdf_host": (C.c_int, [_vp, _i32, C.c_uint64, _fp, _fp, _fp, _fp]),
     "vh_sample_lattice": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _vp]),
+    "vh_cast_rays": (C.c_int, [_vp, C.c_uint64, _vp, _fp, _vp, _vp, _vp]),
+    "vh_cast_rays_host": (C.c_int, [_vp, C.c_uint64, _fp, _fp, _fp, _fp, C.POINTER(_i32)]),
     "vh_export_views": (C.c_int, [_vp, _fp, C.c_int32, _f, _f, _vp, C.c_int32, _vp]),
     "vh_import_view": (C.c_int, [_vp, _vp, C.c_int32]),
     "vh_synchronize": (C.c_int, [_vp]),

@@ -172,6 +172,17 @@ void SDF_Hashtable::sampleSdf(const std::vector<float> &points, int mode, std::v
                              gradient ? gradient->data() : nullptr), "sampleSdf");
 }
 
+void SDF_Hashtable::castRays(const std::vector<float> &rays, const float *depthPlane, std::vector<float> &t, std::vector<float> *normals,
+                             std::vector<int32_t> *voxels)
+{
+    const uint64_t n = rays.size() / 8;
+    t.assign((size_t)n, 0.0f);
+    if (normals) normals->assign((size_t)n * 3, 0.0f);
+    if (voxels) voxels->assign((size_t)n * 4, 0);
+    check(vh_cast_rays_host(ctx_, n, reinterpret_cast<const vh_ray *>(rays.data()), depthPlane, t.data(),
+                            normals ? normals->data() : nullptr, voxels ? voxels->data() : nullptr), "castRays");
+}
+
 uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
 {
     std::vector<float> pos, nrm;

@@ -22,6 +22,8 @@
 //                      LDS, count -> scan -> emit (no counterpart in the reference)
 //   vh_sample.hip      the model as a distance field: sdf / weight / gradient at world points (one point per lane),
 //                      dense boxes of the voxel lattice (one workgroup pass per brick; no counterpart in the reference)
+//   vh_rays.hip        the DDA raycast for arbitrary ray batches: one ray per lane through vh_raycast.hip's per-lane walk
+//                      (no counterpart in the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -45,3 +47,4 @@
 #include "vh_icp.hip"
 #include "vh_mesh.hip"
 #include "vh_sample.hip"
+#include "vh_rays.hip"

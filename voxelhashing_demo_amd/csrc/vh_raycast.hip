@@ -242,11 +242,10 @@ __device__ __forceinline__ bool dda_voxel(const FrameParams &fp, const DevPtrs &
     return s.weight > 0.0f;
 }
 
-// normal of a hit: the TSDF gradient at the hit voxel (central difference where both neighbours are samples, else one-sided,
-// else no normal), normalised, rotated into the camera frame (R^T w), w = 0
-__device__ __forceinline__ float4 dda_normal(const FrameParams &fp, const DevPtrs &dp, int hx, int hy, int hz, int hptr)
+// the TSDF gradient at the hit voxel (central difference where both neighbours are samples, else one-sided, else none),
+// normalised, in the world frame: false (w untouched) where an axis has no neighbour or the length is not > 0
+__device__ __forceinline__ bool dda_gradient(const FrameParams &fp, const DevPtrs &dp, int hx, int hy, int hz, int hptr, float (&w)[3])
 {
-    float4 n = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const int kx = hx >> 3, ky = hy >> 3, kz = hz >> 3;
     float here = 0.0f, g[3] = {0.0f, 0.0f, 0.0f};
     bool ok = dda_voxel(fp, dp, hx, hy, hz, kx, ky, kz, hptr, here);
@@ -260,14 +259,22 @@ __device__ __forceinline__ float4 dda_normal(const FrameParams &fp, const DevPtr
         else if (hm) g[a] = here - sm;
         else ok = false;
     }
-    if (ok) {
-        const float len = __builtin_sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-        if (len > 0.0f) {
-            const float w0 = g[0] / len, w1 = g[1] / len, w2 = g[2] / len;
-            n.x = fp.T[0] * w0 + fp.T[4] * w1 + fp.T[8] * w2;          // R^T * w: world -> camera
-            n.y = fp.T[1] * w0 + fp.T[5] * w1 + fp.T[9] * w2;
-            n.z = fp.T[2] * w0 + fp.T[6] * w1 + fp.T[10] * w2;
-        }
+    if (!ok) return false;
+    const float len = __builtin_sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    if (!(len > 0.0f)) return false;
+    w[0] = g[0] / len; w[1] = g[1] / len; w[2] = g[2] / len;
+    return true;
+}
+
+// normal of a hit: that gradient rotated into the camera frame (R^T w), w = 0; zeros where there is none
+__device__ __forceinline__ float4 dda_normal(const FrameParams &fp, const DevPtrs &dp, int hx, int hy, int hz, int hptr)
+{
+    float4 n = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float w[3];
+    if (dda_gradient(fp, dp, hx, hy, hz, hptr, w)) {
+        n.x = fp.T[0] * w[0] + fp.T[4] * w[1] + fp.T[8] * w[2];          // R^T * w: world -> camera
+        n.y = fp.T[1] * w[0] + fp.T[5] * w[1] + fp.T[9] * w[2];
+        n.z = fp.T[2] * w[0] + fp.T[6] * w[1] + fp.T[10] * w[2];
     }
     return n;
 }
@@ -424,8 +431,11 @@ struct DdaHit {
 //     sequences (a block's crossing is the voxel event out of its last coordinate), so no lane waits for another
 //     lane's phase; kDdaK cells ahead are enumerated by arithmetic alone, their loads issued together, then judged
 //     in order; voxel coordinates are rebuilt only when an allocated block is entered from an absent one.
-template <int kDdaK>      // cells enumerated ahead per round: 2 in the per-lane kernel, 1 where the walk is a rare fall-back (fewer registers)
-__device__ __forceinline__ DdaHit dda_lane_walk(const FrameParams &fp, const DevPtrs &dp, const RaycastArgs &ra, const DdaAxis (&ax)[3],
+// kArgs: where tMax, zrow (the plane that places the samples) and budget come from -- RaycastArgs, uniform over the view, or
+// RayWalkArgs (vh_rays.hip), the ray's own in registers.
+template <int kDdaK,      // cells enumerated ahead per round: 2 in the per-lane kernels, 1 where the walk is a rare fall-back (fewer registers)
+          class kArgs>
+__device__ __forceinline__ DdaHit dda_lane_walk(const FrameParams &fp, const DevPtrs &dp, const kArgs &ra, const DdaAxis (&ax)[3],
                                                 const int (&c)[3], bool live)
 {
     const int prio[3] = {2, 0, 1};

@@ -54,6 +54,22 @@ def preprocess(depth_u16, k_inv, positions, normals, stream=None):
     return positions, normals
 
 
+def pinhole_rays(pose, fx, fy, cx, cy, W, H, t_min, t_max):
+    """The rays of vh_raycast's view as vh_cast_rays takes them: [H * W, 8] float32 (origin, t_min, direction, t_max), row-major
+    over the image, with the raycast's own rounding -- dx = (u - cx) / fx, dy = (v - cy) / fy, D_a = (T[a,0] * dx + T[a,1] * dy)
+    + T[a,2], origin = the pose's translation -- in numpy float32, every operation rounded on its own."""
+    F = np.float32
+    T = np.asarray(pose, F).reshape(4, 4)
+    v, u = np.divmod(np.arange(int(W) * int(H)), int(W))
+    dx, dy = (u.astype(F) - F(cx)) / F(fx), (v.astype(F) - F(cy)) / F(fy)
+    rays = np.empty((len(u), 8), F)
+    for a in range(3):
+        rays[:, a] = T[a, 3]
+        rays[:, 4 + a] = (T[a, 0] * dx + T[a, 1] * dy) + T[a, 2]
+    rays[:, 3], rays[:, 7] = F(t_min), F(t_max)
+    return rays
+
+
 class SDFHashtable:
     """One voxel-hash table on one GPU.
 
@@ -311,6 +327,45 @@ class SDFHashtable:
             w = torch.empty(shape, dtype=torch.float32, device="cuda") if weight else None
         self.sample_lattice_into(lo, dims, sdf, w)
         return (sdf, w) if weight else sdf
+
+    # ---- the model met by rays ----
+    def cast_rays_into(self, rays, t, normals=None, voxels=None, depth_plane=None, n: int = None):
+        """vh_cast_rays into caller-owned device buffers: rays [n, 8] float32 (origin, t_min, direction, t_max; 16-byte
+        aligned), t [n], normals [n, 3] float32 or None, voxels [n, 4] int32 or None; depth_plane: four host floats (one
+        plane places the samples of all rays: row 2 of a pose's inverse gives vh_raycast's depths) or None (along each ray).
+        Asynchronous on the context's stream."""
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("rays must be a float32 tensor [n, 8]")
+        n = int(rays.shape[0]) if n is None else int(n)
+        if not 0 <= n <= rays.shape[0]:
+            raise ValueError(f"n = {n} but rays holds {rays.shape[0]}")
+        for name, buf, dtype, per in (("t", t, torch.float32, 1), ("normals", normals, torch.float32, 3),
+                                      ("voxels", voxels, torch.int32, 4)):
+            if buf is None and name != "t":
+                continue
+            if buf is None or buf.dtype != dtype or buf.numel() < per * n:
+                raise ValueError(f"{name} must be a {dtype} tensor of at least {per} * n = {per * n} elements")
+        plane = None
+        if depth_plane is not None:
+            p = np.ascontiguousarray(np.asarray(depth_plane, np.float32).reshape(4))
+            plane = p.ctypes.data_as(C.POINTER(C.c_float))
+        L.check(self._lib.vh_cast_rays(self._h, n, _dev_ptr(rays), plane, _dev_ptr(t), _dev_ptr(normals), _dev_ptr(voxels)),
+                "vh_cast_rays")
+        return t
+
+    def cast_rays(self, rays, depth_plane=None, normals: bool = False, voxels: bool = False):
+        """Where the rays [n, 8] (float32 CUDA tensor: origin, t_min, direction, t_max) meet the surface: t [n] (NaN where
+        they do not), then the world-frame normals [n, 3] and the hit voxels with the status word [n, 4] (int32; 1 hit, 0 miss,
+        -1 refused) when asked for, as CUDA tensors; a tuple when more than one."""
+        import torch
+        n = int(rays.shape[0])
+        t = torch.empty((n,), dtype=torch.float32, device=rays.device)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=rays.device) if normals else None
+        vox = torch.empty((n, 4), dtype=torch.int32, device=rays.device) if voxels else None
+        self.cast_rays_into(rays, t, nrm, vox, depth_plane)
+        out = (t,) + ((nrm,) if normals else ()) + ((vox,) if voxels else ())
+        return out if len(out) > 1 else t
 
     def device_index(self) -> int:
         """Ordinal of the device the context lives on."""
