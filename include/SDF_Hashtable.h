@@ -104,6 +104,14 @@ public:
      * Synchronises. */
     void castRays(const std::vector<float> &rays, const float *depthPlane, std::vector<float> &t, std::vector<float> *normals = nullptr,
                   std::vector<int32_t> *voxels = nullptr);
+    /* Taking a fused frame back out (vh_deintegrate*, voxelhash.h "taking a frame back out"): the TSDF update run backwards
+     * over the blocks `oldPose` sees, with the frame the pose went in with.  The exact inverse only below the weight cap, with
+     * the options of the original frame, up to fp32 rounding; a voxel left with less than half a sample becomes {0, 0}.
+     * garbageCollect() directly afterwards frees the blocks the removal emptied.  Asynchronous. */
+    void deintegrate(const float4x4 &oldPose, const vh_float4 *d_verts);
+    void deintegrateDepth(const float4x4 &oldPose, const uint16_t *d_depth, const float kInv[9]);
+    /* ... and in again at the corrected pose: deintegrateDepth(oldPose) + integrate(newPose) */
+    void reintegrateDepth(const float4x4 &oldPose, const float4x4 &newPose, const uint16_t *d_depth, const float kInv[9]);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

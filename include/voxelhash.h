@@ -718,6 +718,48 @@ int vh_cast_rays_host(vh_context *ctx, uint64_t n, const vh_ray *h_rays, const f
                       float *h_normals, int32_t *h_voxels);
 
 /* ------------------------------------------------------------------ */
+/* taking a frame back out                                             */
+/* ------------------------------------------------------------------ */
+/* De-integration: the TSDF update of a fused frame run backwards, so that a frame whose pose was corrected after the fact can
+ * be removed at its OLD pose and fused again at the new one without rebuilding the model (BundleFusion's deIntegrate on this
+ * data structure; tests/deintegrate_ref.py is the rule in executable form).  IEEE fp32, every multiply and add
+ * rounded on its own, in the order written here: the same model, frame and options give the same bits.
+ *   Block set: every allocated entry of this table (or shard) that passes blockInFrustum for `pose` -- exactly the compact
+ *     set vh_set_pose(pose) + vh_flatten produce, chained overflow entries included.  No block is allocated or freed.
+ *   Sample: for each of a block's 512 voxels the frame's sample (s, cw) is computed exactly as vh_integrate's update does:
+ *     the camera point by the context's semantics, project, the image bounds test, depth <= 0 rejects, s = depth - cz,
+ *     trunc = truncation (+ truncScale * depth with the option depth_truncation AS IT IS SET NOW), !(s > -trunc) rejects,
+ *     s clamped to [-trunc, trunc], cw = 0.1f (or max((float)(integrationWeightSample * 1.5 * (1 - (depth - 0.5f) / 4.5f)), 1)
+ *     with the option weight_sample, the product in double).  A voxel the update would have skipped is untouched.
+ *   Stored weight: with the stored voxel {os, ow}, a voxel with !(ow > 0) is untouched.
+ *   Removal: nw = ow - cw.  floor = half the smallest weight a sample can have: 0.05f, or 0.5f with weight_sample.
+ *     !(nw >= floor): the voxel becomes {+0.0f, +0.0f}, the zero-initialised state, which the mesh, the sampler and the raycasts
+ *     treat as invalid.  Otherwise sdf = ((os * ow) - (s * cw)) / nw and weight = nw.  (k additions of 0.1f followed by k
+ *     subtractions leave a rounding residue, not 0: a residue is far below half a sample, a sample that genuinely remains is
+ *     never below a whole one.)
+ *   Exactness: this is the algebraic inverse of the update only for voxels whose weight never reached integrationWeightMax
+ *     (the cap forgets how much was added), only when the options are those the frame went in with, and even then only up to
+ *     fp32 rounding: sdf and weight of the remaining frames come back to within rounding, not to the bit.  Blocks that were
+ *     allocated AFTER the original frame and that the old view sees receive a subtraction they never got an addition for, as
+ *     in BundleFusion.  One case is exact: a frame integrated into an empty model and then taken out leaves every voxel {0, 0}.
+ * vh_deintegrate is the counterpart of vh_integrate's update for a float4 vertex map (it reads .z).  vh_deintegrate_depth is
+ * the counterpart of vh_integrate_depth, straight from the uint16 image: the bits of vh_preprocess + vh_deintegrate.
+ * vh_reintegrate_depth is exactly vh_deintegrate_depth(old_pose) followed by vh_integrate_depth(new_pose).
+ * The calls only enqueue work on the context's stream, behind every frame queued so far (a pending pipelined frame is
+ * launched first); they read nothing back and do not synchronise.  The context's pose becomes `pose`; afterwards the compact
+ * list and vh_counters.occupied are those of vh_set_pose(pose) + vh_flatten -- the blocks the call touched -- so a
+ * vh_garbage_collect directly after the call frees the blocks the removal emptied (the pairing to use).  The lock epoch, the
+ * heap and the hash table are unchanged.  Both semantics; with or without the overflow list; on shards (vh_create_shard) every
+ * shard is called with the same pose and image and removes from its own blocks.  In vh_kernel_times the launch counts as a
+ * TSDF update (integrate_ms), its flatten as flatten_ms.
+ * VH_ERR_INVALID_ARGUMENT: a NULL context, pose, image or k_inv; a context that holds an imported view (vh_import_view(s)):
+ * its voxels live in the caller's records.  A refused call changes nothing. */
+int vh_deintegrate(vh_context *ctx, const float pose[16], const vh_float4 *d_verts);
+int vh_deintegrate_depth(vh_context *ctx, const float pose[16], const uint16_t *d_depth, const float k_inv[9]);
+int vh_reintegrate_depth(vh_context *ctx, const float old_pose[16], const float new_pose[16],
+                         const uint16_t *d_depth, const float k_inv[9]);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to

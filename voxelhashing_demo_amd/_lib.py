@@ -145,6 +145,9 @@ SIGNATURES = {
     "vh_sample_lattice": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _vp]),
     "vh_cast_rays": (C.c_int, [_vp, C.c_uint64, _vp, _fp, _vp, _vp, _vp]),
     "vh_cast_rays_host": (C.c_int, [_vp, C.c_uint64, _fp, _fp, _fp, _fp, C.POINTER(_i32)]),
+    "vh_deintegrate": (C.c_int, [_vp, _fp, _vp]),
+    "vh_deintegrate_depth": (C.c_int, [_vp, _fp, _vp, _fp]),
+    "vh_reintegrate_depth": (C.c_int, [_vp, _fp, _fp, _vp, _fp]),
     "vh_export_views": (C.c_int, [_vp, _fp, C.c_int32, _f, _f, _vp, C.c_int32, _vp]),
     "vh_import_view": (C.c_int, [_vp, _vp, C.c_int32]),
     "vh_synchronize": (C.c_int, [_vp]),

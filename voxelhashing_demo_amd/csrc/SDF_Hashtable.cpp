@@ -183,6 +183,21 @@ void SDF_Hashtable::castRays(const std::vector<float> &rays, const float *depthP
                             normals ? normals->data() : nullptr, voxels ? voxels->data() : nullptr), "castRays");
 }
 
+void SDF_Hashtable::deintegrate(const float4x4 &oldPose, const vh_float4 *d_verts)
+{
+    check(vh_deintegrate(ctx_, oldPose.entries, d_verts), "deintegrate");
+}
+
+void SDF_Hashtable::deintegrateDepth(const float4x4 &oldPose, const uint16_t *d_depth, const float kInv[9])
+{
+    check(vh_deintegrate_depth(ctx_, oldPose.entries, d_depth, kInv), "deintegrateDepth");
+}
+
+void SDF_Hashtable::reintegrateDepth(const float4x4 &oldPose, const float4x4 &newPose, const uint16_t *d_depth, const float kInv[9])
+{
+    check(vh_reintegrate_depth(ctx_, oldPose.entries, newPose.entries, d_depth, kInv), "reintegrateDepth");
+}
+
 uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
 {
     std::vector<float> pos, nrm;

@@ -568,6 +568,7 @@ static int ensure_candidates(vh_context *c, size_t need)
 #include "vh_api_mesh.hip"
 #include "vh_api_sample.hip"
 #include "vh_api_rays.hip"
+#include "vh_api_deintegrate.hip"
 #include "vh_api_dropin.hip"
 #include "vh_api_icp.hip"
 #include "vh_api_dist.hip"

@@ -24,6 +24,8 @@
 //                      dense boxes of the voxel lattice (one workgroup pass per brick; no counterpart in the reference)
 //   vh_rays.hip        the DDA raycast for arbitrary ray batches: one ray per lane through vh_raycast.hip's per-lane walk
 //                      (no counterpart in the reference)
+//   vh_deintegrate.hip de-integration: the TSDF update run backwards for one frame over the blocks its old pose sees, in
+//                      integrate_block's shape (BundleFusion's deIntegrate; no counterpart in the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -48,3 +50,4 @@
 #include "vh_mesh.hip"
 #include "vh_sample.hip"
 #include "vh_rays.hip"
+#include "vh_deintegrate.hip"

@@ -152,6 +152,52 @@ class SDFHashtable:
         L.check(self._lib.vh_integrate_depth(self._h, pp, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float))),
                 "vh_integrate_depth")
 
+    # ---- taking a frame back out ----
+    def _check_verts(self, verts, what):
+        if not isinstance(verts, int):
+            import torch
+            if verts.dtype != torch.float32:
+                raise ValueError(f"{what}: the vertex map must be float32")
+            if verts.numel() != self.width * self.height * 4:
+                raise ValueError(f"{what}: the vertex map must hold height * width float4 vertices")
+            if not verts.is_cuda:
+                raise ValueError(f"{what}: the vertex map must be a CUDA tensor")
+
+    def _check_depth_u16(self, depth_u16, what):
+        if not isinstance(depth_u16, int):
+            import torch
+            if depth_u16.dtype != torch.uint16:
+                raise ValueError(f"{what}: the sensor image must be uint16")
+            if depth_u16.numel() != self.width * self.height:
+                raise ValueError(f"{what}: the sensor image must hold height * width pixels")
+            if not depth_u16.is_cuda:
+                raise ValueError(f"{what}: the sensor image must be a CUDA tensor")
+
+    def deintegrate(self, pose, verts):
+        """Asynchronous: the TSDF update of integrate(pose, verts) run backwards over the blocks `pose` sees.  The exact inverse
+        only below the weight cap and with the frame's options, up to fp32 rounding; garbage_collect() directly afterwards
+        frees the blocks the removal emptied."""
+        _, pp = _pose16(pose)
+        self._check_verts(verts, "deintegrate")
+        L.check(self._lib.vh_deintegrate(self._h, pp, _dev_ptr(verts)), "vh_deintegrate")
+
+    def deintegrate_depth(self, pose, depth_u16, k_inv):
+        """The same straight from the uint16 sensor image [H, W] (== preprocess + deintegrate)."""
+        _, pp = _pose16(pose)
+        self._check_depth_u16(depth_u16, "deintegrate_depth")
+        k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        L.check(self._lib.vh_deintegrate_depth(self._h, pp, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float))),
+                "vh_deintegrate_depth")
+
+    def reintegrate_depth(self, old_pose, new_pose, depth_u16, k_inv):
+        """deintegrate_depth(old_pose) + integrate_depth(new_pose): a frame moved to its corrected pose."""
+        _, po = _pose16(old_pose)
+        _, pn = _pose16(new_pose)
+        self._check_depth_u16(depth_u16, "reintegrate_depth")
+        k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        L.check(self._lib.vh_reintegrate_depth(self._h, po, pn, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float))),
+                "vh_reintegrate_depth")
+
     def integrate_batch(self, poses, verts_list, normals_list=None):
         """len(poses) frames in len(poses) + 1 launches (pipelined frames, flushed at the end); equals
         integrate() frame by frame."""
