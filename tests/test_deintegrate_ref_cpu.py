@@ -25,7 +25,8 @@ def bits(v):
 
 @pytest.mark.parametrize("sem,pose_name,flags,scene", GOLDEN_CASES)
 def test_plus_one_is_the_oracles_update(oracle, sem, pose_name, flags, scene):
-    """The restated sample computation and combineVoxel against OracleTable.integrate_depth_map on the golden scenes
+    """The numpy form of the sample computation (on the device it is stated once, tsdf_apply in vh_integrate.hip, for the
+    update and for the removal) and combineVoxel against OracleTable.integrate_depth_map on the golden scenes
     (640x480 spheres, 2^17 buckets): first into an empty model, then onto stored weights."""
     pose = I4 if pose_name == "I" else POSE
     verts = synth.sphere_inside_scene() if scene == "inside" else synth.sphere_outside_scene()

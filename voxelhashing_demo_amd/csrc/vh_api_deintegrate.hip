@@ -1,5 +1,5 @@
 // vh_api_deintegrate.hip -- C-ABI, taking a frame back out: vh_deintegrate, vh_deintegrate_depth, vh_reintegrate_depth
-// (kernel: vh_deintegrate.hip).  Included by vh_api.hip (same translation unit: shares fail(), VH_HIP, DeviceGuard,
+// (kernel: vh_integrate.hip).  Included by vh_api.hip (same translation unit: shares fail(), VH_HIP, DeviceGuard,
 // launch(), flush_pending(), vh_set_pose(), vh_flatten()).
 // The calls only enqueue: no scratch, no read-back, no synchronisation.
 

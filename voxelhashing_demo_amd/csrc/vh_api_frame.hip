@@ -522,16 +522,14 @@ extern "C" int vh_integrate_depth(vh_context *c, const float pose[16], const uin
     return run_frame(c, in, DepthSensor{in.depth, in.k[6], in.k[7], in.k[8], in.unit});
 }
 
-// K frames in K + 1 launches: the pipeline switched on for the call, flushed at its end.
-extern "C" int vh_integrate_batch(vh_context *c, int32_t count, const float *poses, const vh_float4 *const *d_verts,
-                                  const vh_float4 *const *d_normals)
+// K frames in K + 1 launches: the pipeline switched on for the call, flushed at its end.  frame(i): frame i's entry point.
+template <class Frame>
+static int run_batch(vh_context *c, int32_t count, Frame frame)
 {
-    if (!c || count < 0 || (count > 0 && (!poses || !d_verts))) return fail(VH_ERR_INVALID_ARGUMENT, "bad argument");
     const int saved = c->pipeline;
     c->pipeline = 1;
     int rc = VH_OK;
-    for (int32_t i = 0; i < count && rc == VH_OK; ++i)
-        rc = vh_integrate(c, poses + 16 * (size_t)i, d_verts[i], d_normals ? d_normals[i] : nullptr);
+    for (int32_t i = 0; i < count && rc == VH_OK; ++i) rc = frame(i);
     c->pipeline = saved;
     if (!saved) {
         const int rc2 = vh_flush(c);
@@ -540,20 +538,18 @@ extern "C" int vh_integrate_batch(vh_context *c, int32_t count, const float *pos
     return rc;
 }
 
+extern "C" int vh_integrate_batch(vh_context *c, int32_t count, const float *poses, const vh_float4 *const *d_verts,
+                                  const vh_float4 *const *d_normals)
+{
+    if (!c || count < 0 || (count > 0 && (!poses || !d_verts))) return fail(VH_ERR_INVALID_ARGUMENT, "bad argument");
+    return run_batch(c, count, [&](int32_t i) { return vh_integrate(c, poses + 16 * (size_t)i, d_verts[i], d_normals ? d_normals[i] : nullptr); });
+}
+
 extern "C" int vh_integrate_depth_batch(vh_context *c, int32_t count, const float *poses, const uint16_t *const *d_depth,
                                         const float k_inv[9])
 {
     if (!c || count < 0 || (count > 0 && (!poses || !d_depth || !k_inv))) return fail(VH_ERR_INVALID_ARGUMENT, "bad argument");
-    const int saved = c->pipeline;
-    c->pipeline = 1;
-    int rc = VH_OK;
-    for (int32_t i = 0; i < count && rc == VH_OK; ++i) rc = vh_integrate_depth(c, poses + 16 * (size_t)i, d_depth[i], k_inv);
-    c->pipeline = saved;
-    if (!saved) {
-        const int rc2 = vh_flush(c);
-        if (rc == VH_OK) rc = rc2;
-    }
-    return rc;
+    return run_batch(c, count, [&](int32_t i) { return vh_integrate_depth(c, poses + 16 * (size_t)i, d_depth[i], k_inv); });
 }
 
 // The raycast in the context's mode (option "raycast_mode"): the voxel DDA (default), optionally with the normal
@@ -593,11 +589,11 @@ static int raycast_impl(vh_context *c, const float pose[16], float t_min, float 
         // or beyond 2^22 steps is refused (the oracle walks at most that many voxels per ray).
         const double mdx = std::max(std::fabs((0.0 - ra.cx) / ra.fx), std::fabs(((double)fp.width - 1.0 - ra.cx) / ra.fx));
         const double mdy = std::max(std::fabs((0.0 - ra.cy) / ra.fy), std::fabs(((double)fp.height - 1.0 - ra.cy) / ra.fy));
-        double steps = 16.0;
+        double bound[3];                           // |T_a0| max|dx| + |T_a1| max|dy| + |T_a2|
         for (int a = 0; a < 3; ++a)
-            steps += 1.01 * ((double)t_max - (double)t_min) *
-                     (std::fabs((double)pose[4 * a]) * mdx + std::fabs((double)pose[4 * a + 1]) * mdy + std::fabs((double)pose[4 * a + 2])) /
-                     (double)fp.voxelSize + 2.0;
+            bound[a] = std::fabs((double)pose[4 * a]) * mdx + std::fabs((double)pose[4 * a + 1]) * mdy + std::fabs((double)pose[4 * a + 2]);
+        double steps = 16.0;
+        for (int a = 0; a < 3; ++a) steps += 1.01 * ((double)t_max - (double)t_min) * bound[a] / (double)fp.voxelSize + 2.0;
         if (!(steps < 4194304.0)) return fail(VH_ERR_INVALID_ARGUMENT, "view too deep for the voxel size (more than 2^22 voxel steps per ray) or not finite");
         ra.budget = (int)steps;
         // The camera centre in voxel-grid units, and the domain: inside an allocated block the kernel steps the voxel
@@ -605,11 +601,8 @@ static int raycast_impl(vh_context *c, const float pose[16], float t_min, float 
         double reach = 0.0;
         for (int a = 0; a < 3; ++a) {
             ra.G[a] = pose[4 * a + 3] / fp.voxelSize + 0.5f;
-            reach = std::max(reach, std::fabs((double)ra.G[a]) + std::fabs((double)t_max) *
-                                        (std::fabs((double)pose[4 * a]) * mdx + std::fabs((double)pose[4 * a + 1]) * mdy +
-                                         std::fabs((double)pose[4 * a + 2])) / (double)fp.voxelSize + std::fabs((double)t_min) *
-                                        (std::fabs((double)pose[4 * a]) * mdx + std::fabs((double)pose[4 * a + 1]) * mdy +
-                                         std::fabs((double)pose[4 * a + 2])) / (double)fp.voxelSize);
+            reach = std::max(reach, std::fabs((double)ra.G[a]) + std::fabs((double)t_max) * bound[a] / (double)fp.voxelSize +
+                                        std::fabs((double)t_min) * bound[a] / (double)fp.voxelSize);
         }
         if (!(reach < 8388608.0)) return fail(VH_ERR_INVALID_ARGUMENT, "view reaches beyond 2^23 voxels from the origin");
         ra.invVs = 1.0f / fp.voxelSize;

@@ -362,4 +362,9 @@ __device__ __forceinline__ uint32_t find_entry_overflow(const FrameParams &fp, c
     return ~0u;
 }
 
+// Workgroups are handed to the 8 XCDs round robin (workgroup b runs on XCD b % 8, each with its own L2).  Renumbered this
+// way (n workgroups, n a multiple of 8 -- the caller's to ensure) an XCD gets a contiguous eighth of the indices.
+template <class I>
+__device__ __forceinline__ I xcd_contiguous(I b, I n) { return (b & 7) * (n >> 3) + (b >> 3); }
+
 }  // namespace vh

@@ -1,4 +1,4 @@
-// vh_integrate.hip -- integrateDepthMap: 8^3-block TSDF update.
+// vh_integrate.hip -- integrateDepthMap: 8^3-block TSDF update, and the same update run backwards (de-integration).
 // Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after vh_device.h.
 #pragma once
 
@@ -37,10 +37,18 @@ struct DepthSensor {
     }
 };
 
-template <class Depth>
-__device__ __forceinline__ bool tsdf_update(const FrameParams &fp, const float *Tinv, const Depth &src, int vx, int vy,
-                                            int vz, float &sdfOut, float &wOut)
+// The one statement of the frame's TSDF sample (s, cw) of voxel (vx, vy, vz), with two compile-time tails: kTsdfAdd combines it
+// into the stored voxel {sdfIO, wIO} (combineVoxel), kTsdfRemove takes it back out (de-integration: include/voxelhash.h states
+// the rule, tests/deintegrate_ref.py is its executable form; BundleFusion's deIntegrate is the model, the reference has none).
+// true: the voxel changed.  The line numbers are VoxelUtils.cu's.
+enum TsdfOp { kTsdfAdd, kTsdfRemove };
+
+template <TsdfOp kOp, class Depth>
+__device__ __forceinline__ bool tsdf_apply(const FrameParams &fp, const float *Tinv, const Depth &src, int vx, int vy,
+                                           int vz, float &sdfIO, float &wIO)
 {
+    // removal: a voxel that holds nothing is left before its sample is computed; the outcome is the same, untouched
+    if constexpr (kOp == kTsdfRemove) { if (!(wIO > 0.0f)) return false; }
     float cx, cy, cz;
     if (fp.semantics == VH_SEM_REFERENCE) {
         // VoxelUtils.cu:797-800: inverse pose on the voxel INDEX, truncate, then metres
@@ -68,29 +76,70 @@ __device__ __forceinline__ bool tsdf_update(const FrameParams &fp, const float *
         const float zeroOne = (depth - 0.5f) / (5.0f - 0.5f);
         cw = __builtin_fmaxf((float)((double)fp.weightSample * 1.5 * (1.0 - (double)zeroOne)), 1.0f);
     }
-    // combineVoxel, :779-787
-    const float ow = wOut, os = sdfOut;
-    sdfOut = ((os * ow) + (sdf * cw)) / (ow + cw);
-    wOut = __builtin_fminf(fp.weightMax, ow + cw);
+    const float ow = wIO, os = sdfIO;
+    if constexpr (kOp == kTsdfAdd) {
+        // combineVoxel, :779-787
+        sdfIO = ((os * ow) + (sdf * cw)) / (ow + cw);
+        wIO = __builtin_fminf(fp.weightMax, ow + cw);
+    } else {
+        // wFloor: half the smallest weight a sample can have -- what k additions followed by k subtractions of the same
+        // weights leave is a rounding residue far below it, a sample that genuinely remains is a whole one.
+        const float wFloor = (fp.flags & kFlagWeightSample) ? 0.5f : 0.05f;
+        const float nw = ow - cw;
+        if (!(nw >= wFloor)) {
+            sdfIO = 0.0f;              // the zero-initialised state: invalid to the mesh, the sampler and the raycast
+            wIO = 0.0f;
+            return true;
+        }
+        sdfIO = ((os * ow) - (sdf * cw)) / nw;
+        wIO = nw;
+    }
     return true;
 }
 
-// the 256 lanes of a workgroup update the 8^3 block of entry e; the depth comes from the float4
-// vertex map (DepthPlane on &verts[0].z) or straight from the sensor image (DepthSensor)
+template <class Depth>
+__device__ __forceinline__ bool tsdf_update(const FrameParams &fp, const float *Tinv, const Depth &src, int vx, int vy,
+                                            int vz, float &sdfIO, float &wIO)
+{
+    return tsdf_apply<kTsdfAdd>(fp, Tinv, src, vx, vy, vz, sdfIO, wIO);
+}
+
+// The lane's share of the 8^3 block of entry e: the 256 lanes of a workgroup take the block, lane t voxels 2t and 2t + 1
+// (neighbours in x) as one 16-byte cell {sdf0, w0, sdf1, w1}; (bx, by, bz) is the first of the two.
+struct LaneCell {
+    float4 *cell;
+    int bx, by, bz;
+};
+
+__device__ __forceinline__ LaneCell lane_cell(const DevPtrs &dp, const VoxelEntry &e)
+{
+    const int lin = 2 * (int)threadIdx.x;        // linearizeVoxelPos: z*64 + y*8 + x  (:311-317)
+    const int tx = lin & 7, ty = (lin >> 3) & 7, tz = lin >> 6;
+    LaneCell c;
+    c.bx = (int)((uint32_t)e.pos[0] * 8u) + tx;  // block2Voxel + threadIdx (:793-796)
+    c.by = (int)((uint32_t)e.pos[1] * 8u) + ty;
+    c.bz = (int)((uint32_t)e.pos[2] * 8u) + tz;
+    c.cell = reinterpret_cast<float4 *>(dp.blocks + (size_t)e.ptr + lin);
+    return c;
+}
+
+// one 16-byte load, the two voxels updated (kTsdfAdd) or taken back out (kTsdfRemove), one 16-byte store when one of them changed
+template <TsdfOp kOp, class Depth>
+__device__ __forceinline__ void update_block(const FrameParams &fp, const DevPtrs &dp, const VoxelEntry &e, const Depth &src)
+{
+    const LaneCell c = lane_cell(dp, e);
+    float4 v = *c.cell;
+    const bool u0 = tsdf_apply<kOp>(fp, fp.Tinv, src, c.bx, c.by, c.bz, v.x, v.y);
+    const bool u1 = tsdf_apply<kOp>(fp, fp.Tinv, src, c.bx + 1, c.by, c.bz, v.z, v.w);
+    if (u0 || u1) *c.cell = v;
+}
+
+// the depth comes from the float4 vertex map (DepthPlane on &verts[0].z) or straight from the sensor image (DepthSensor)
 template <class Depth>
 __device__ __forceinline__ void integrate_block(const FrameParams &fp, const DevPtrs &dp, const VoxelEntry &e,
                                                 const Depth &src)
 {
-    const int lin = 2 * (int)threadIdx.x;        // linearizeVoxelPos: z*64 + y*8 + x  (:311-317)
-    const int tx = lin & 7, ty = (lin >> 3) & 7, tz = lin >> 6;
-    const int bx = (int)((uint32_t)e.pos[0] * 8u) + tx;     // block2Voxel + threadIdx (:793-796)
-    const int by = (int)((uint32_t)e.pos[1] * 8u) + ty;
-    const int bz = (int)((uint32_t)e.pos[2] * 8u) + tz;
-    float4 *cell = reinterpret_cast<float4 *>(dp.blocks + (size_t)e.ptr + lin);
-    float4 v = *cell;                            // {sdf0, w0, sdf1, w1}
-    const bool u0 = tsdf_update(fp, fp.Tinv, src, bx, by, bz, v.x, v.y);
-    const bool u1 = tsdf_update(fp, fp.Tinv, src, bx + 1, by, bz, v.z, v.w);
-    if (u0 || u1) *cell = v;
+    update_block<kTsdfAdd>(fp, dp, e, src);
 }
 
 // The blocks list[first], list[first + stride], ... < count, one per workgroup pass.
@@ -104,15 +153,15 @@ __device__ __forceinline__ void integrate_block(const FrameParams &fp, const Dev
 // 71.4 vs 70.3, loaded C2 26.2 vs 25.6, walk-free C3 29.4 vs 27.3: every voxel is read once and written once by the same
 // lane, so there is no reuse for LDS to serve (north_star's "one 8^3 block staged into LDS per workgroup" is therefore an
 // accepted, measured deviation: README.md; the code is in git history, DESIGN_LOG.md names the commit).
-template <class Depth>
 // countB > 0: the list has two ends (CompactOut, vh_walk.hip): entries 0 .. count-1 from the front, countB more
 // from the back of the numEntries-entry buffer
+template <class Depth, TsdfOp kOp = kTsdfAdd>
 __device__ __forceinline__ void integrate_list(const FrameParams &fp, const DevPtrs &dp, const VoxelEntry *__restrict__ list,
                                                int count, int first, int stride, const Depth &src, int countB = 0,
                                                uint32_t numEntries = 0)
 {
     for (int k = first; k < count + countB; k += stride)
-        integrate_block(fp, dp, k < count ? list[k] : list[numEntries - 1u - (uint32_t)(k - count)], src);
+        update_block<kOp>(fp, dp, k < count ? list[k] : list[numEntries - 1u - (uint32_t)(k - count)], src);
 }
 
 // The dense list of the boundary: end B of a two-ended list moved behind end A and what the commit phase appended
@@ -148,6 +197,14 @@ template <class Depth>
 __global__ __launch_bounds__(256) void integrate_kernel(const FrameParams fp, const DevPtrs dp, const Depth verts)
 {
     integrate_list(fp, dp, dp.compact, dp.counters[kCompactCount], (int)blockIdx.x, (int)gridDim.x, verts);
+}
+
+// De-integration: the same fixed grid over the dense compact list the step-level flatten left for the frame's OLD pose
+// (entries of allocated blocks only, so every e.ptr names a whole block inside dp.blocks), each sample taken back out.
+template <class Depth>
+__global__ __launch_bounds__(256) void deintegrate_kernel(const FrameParams fp, const DevPtrs dp, const Depth src)
+{
+    integrate_list<Depth, kTsdfRemove>(fp, dp, dp.compact, dp.counters[kCompactCount], (int)blockIdx.x, (int)gridDim.x, src);
 }
 
 }  // namespace vh

@@ -9,7 +9,8 @@
 //                      compaction of allocated in-frustum entries (flattenKernel, :719-749),
 //                      and the walk over the bucket-occupancy bitmap that replaces it by default
 //   vh_integrate.hip   integrateDepthMap: one 8^3 block per workgroup pass, 16-byte-per-lane
-//                      voxel read-modify-write (integrateDepthMapKernel, :790-842)
+//                      voxel read-modify-write (integrateDepthMapKernel, :790-842); de-integration, the same update
+//                      run backwards for one frame (BundleFusion's deIntegrate; no counterpart in the reference)
 //   vh_frame.hip       the fused frame: {claim || walk} and {commit + integrate} in two launches, or pipelined in one
 //   vh_shard.hip       the multi-camera frame on a bucket-range shard
 //   vh_raycast.hip     per-pixel march through the hash (stand-in for SDFRenderer::render,
@@ -24,8 +25,6 @@
 //                      dense boxes of the voxel lattice (one workgroup pass per brick; no counterpart in the reference)
 //   vh_rays.hip        the DDA raycast for arbitrary ray batches: one ray per lane through vh_raycast.hip's per-lane walk
 //                      (no counterpart in the reference)
-//   vh_deintegrate.hip de-integration: the TSDF update run backwards for one frame over the blocks its old pose sees, in
-//                      integrate_block's shape (BundleFusion's deIntegrate; no counterpart in the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -50,4 +49,3 @@
 #include "vh_mesh.hip"
 #include "vh_sample.hip"
 #include "vh_rays.hip"
-#include "vh_deintegrate.hip"

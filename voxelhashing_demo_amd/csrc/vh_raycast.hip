@@ -61,7 +61,7 @@ __device__ __forceinline__ void xcd_tile(int &tx, int &ty)
 {
     const int n = gridDim.x * gridDim.y, b = blockIdx.y * gridDim.x + blockIdx.x;
     if ((n & 7) == 0) {
-        const int r = (b & 7) * (n >> 3) + (b >> 3);
+        const int r = xcd_contiguous(b, n);
         ty = r / (int)gridDim.x;
         tx = r - ty * (int)gridDim.x;
     }
@@ -173,6 +173,25 @@ struct DdaAxis {
     int s;                    // +1 / -1
 };
 
+// the axis of the ray g(t) = G + E*t; invE: as the ray's set-up computed it (the cooperative form keeps it in LDS)
+__device__ __forceinline__ void dda_axis_init(DdaAxis &ax, float G, float E, float invE)
+{
+    ax.G = G;
+    ax.E = E;
+    ax.invE = invE;
+    ax.s = E > 0.0f ? 1 : -1;
+    ax.Gs = E > 0.0f ? G - 1.0f : G;
+}
+
+__device__ __forceinline__ void dda_axis_init(DdaAxis &ax, float G, float E)
+{
+    const bool active = __builtin_fabsf(E) > 1.0e-20f;
+    dda_axis_init(ax, G, E, active ? 1.0f / E : 0.0f);
+}
+
+// the voxel coordinate of the axis at depth t
+__device__ __forceinline__ int dda_coord(const DdaAxis &ax, float t) { return f2i_rz(__builtin_floorf(ax.G + ax.E * t)); }
+
 __device__ __forceinline__ float dda_tnext(const DdaAxis &ax, int c)
 {
     return ax.invE != 0.0f ? ((float)c - ax.Gs) * ax.invE : __builtin_inff();
@@ -190,7 +209,7 @@ __device__ __forceinline__ int dda_advance(const DdaAxis &ax, int prioB, int cur
 {
     if (ax.invE == 0.0f || cur == last) return cur;
     const int lo = min(cur, last), hi = max(cur, last);
-    int e = f2i_rz(__builtin_floorf(ax.G + ax.E * te));
+    int e = dda_coord(ax, te);
     e = min(max(e, lo), hi);
     while (e != last && dda_before(dda_tnext(ax, e), prioB, te, prioX)) e += ax.s;
     while (e != cur && !dda_before(dda_tnext(ax, e - ax.s), prioB, te, prioX)) e -= ax.s;
@@ -202,7 +221,7 @@ __device__ __forceinline__ int dda_advance(const DdaAxis &ax, int prioB, int cur
 __device__ __forceinline__ int dda_start(const DdaAxis &ax, int cur, float tau)
 {
     if (ax.invE == 0.0f) return cur;
-    int e = f2i_rz(__builtin_floorf(ax.G + ax.E * tau));
+    int e = dda_coord(ax, tau);
     e = ax.s > 0 ? max(e, cur) : min(e, cur);
     while (dda_tnext(ax, e) < tau) e += ax.s;
     while (e != cur && !(dda_tnext(ax, e - ax.s) < tau)) e -= ax.s;
@@ -364,13 +383,8 @@ __device__ __forceinline__ void dda_ray(const FrameParams &fp, const RaycastArgs
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float D = fp.T[4 * a + 0] * dx + fp.T[4 * a + 1] * dy + fp.T[4 * a + 2];
-        ax[a].G = ra.G[a];
-        ax[a].E = D / vs;
-        const bool active = __builtin_fabsf(ax[a].E) > 1.0e-20f;
-        ax[a].invE = active ? 1.0f / ax[a].E : 0.0f;
-        ax[a].s = ax[a].E > 0.0f ? 1 : -1;
-        ax[a].Gs = ax[a].E > 0.0f ? ax[a].G - 1.0f : ax[a].G;
-        c[a] = f2i_rz(__builtin_floorf(ax[a].G + ax[a].E * ra.tMin));
+        dda_axis_init(ax[a], ra.G[a], D / vs);
+        c[a] = dda_coord(ax[a], ra.tMin);
     }
 }
 

@@ -178,12 +178,8 @@ __device__ __forceinline__ void coop_walk_item(const FrameParams &fp, const DevP
     int c[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        ax[a].G = ra.G[a];
-        ax[a].E = sh.state[w][a][lane];
-        ax[a].invE = sh.state[w][3 + a][lane];
+        dda_axis_init(ax[a], ra.G[a], sh.state[w][a][lane], sh.state[w][3 + a][lane]);
         c[a] = __float_as_int(sh.state[w][6 + a][lane]);
-        ax[a].s = ax[a].E > 0.0f ? 1 : -1;
-        ax[a].Gs = ax[a].E > 0.0f ? ax[a].G - 1.0f : ax[a].G;
     }
     unsigned long long *word = &sh.best[w][lane];
     const unsigned long long cur = *word;
@@ -350,7 +346,7 @@ __global__ __launch_bounds__(64 * kDdaBlockWaves, VH_DDA_WAVES) void raycast_coo
     // group -> patches: each XCD (workgroup index mod 8, own L2) takes a contiguous run of groups, a group's patches lie
     // `groups` apart in the row-major patch grid
     int g = (int)blockIdx.x;
-    if ((ra.groups & 7) == 0) g = (g & 7) * (ra.groups >> 3) + (g >> 3);
+    if ((ra.groups & 7) == 0) g = xcd_contiguous(g, ra.groups);
     // wave j takes a patch of the j-th quarter of the row-major patch grid (a quarter of the rows further down), rotated inside
     // its quarter by j quarter-rows (a quarter of a row further right): a grazing wall is a vertical band as often as a grazing
     // floor is a horizontal one.  A rotation inside the quarter: every patch is still rendered exactly once.

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kRaysBlock, VH_DDA_WAVES) void cast_rays_kernel(con
                                                                              int32_t *__restrict__ voxelOut)
 {
     const uint32_t nb = gridDim.x, b = blockIdx.x;
-    const uint32_t group = (b & 7u) * (nb >> 3) + (b >> 3);
+    const uint32_t group = xcd_contiguous(b, nb);
     const uint32_t at = group * (uint32_t)kRaysBlock + threadIdx.x;
     if (at >= n) return;
     const float4 r0 = rays[2 * (size_t)at], r1 = rays[2 * (size_t)at + 1];          // origin, t_min; direction, t_max
@@ -64,13 +64,8 @@ __global__ __launch_bounds__(kRaysBlock, VH_DDA_WAVES) void cast_rays_kernel(con
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         ok = ok && __builtin_fabsf(O[a]) < inf && __builtin_fabsf(D[a]) < inf;
-        ax[a].G = O[a] / vs + 0.5f;
-        ax[a].E = D[a] / vs;
-        const bool active = __builtin_fabsf(ax[a].E) > 1.0e-20f;
-        ax[a].invE = active ? 1.0f / ax[a].E : 0.0f;
-        ax[a].s = ax[a].E > 0.0f ? 1 : -1;
-        ax[a].Gs = ax[a].E > 0.0f ? ax[a].G - 1.0f : ax[a].G;
-        c[a] = f2i_rz(__builtin_floorf(ax[a].G + ax[a].E * tMin));
+        dda_axis_init(ax[a], O[a] / vs + 0.5f, D[a] / vs);
+        c[a] = dda_coord(ax[a], tMin);
         const double e = __builtin_fabs((double)D[a]) / (double)vs;
         steps += 1.01 * range * e + 2.0;
         ok = ok && __builtin_fabs((double)ax[a].G) + ends * e < 8388608.0;

@@ -160,6 +160,14 @@ __global__ __launch_bounds__(kFlattenThreads) void flatten_multi_kernel(const Fr
     flatten_multi_tile(fp, dp, numEntries, blockIdx.x, numCams, packets, packetStride, kCompactCount);
 }
 
+// where the camera z of a pixel comes from in camera packet pk (vh_integrate.hip)
+template <bool kSensor>
+__device__ __forceinline__ auto packet_depth(const float *pk)
+{
+    if constexpr (kSensor) return DepthSensor{reinterpret_cast<const uint16_t *>(pk + kPacketHeaderU16), pk[32], pk[33], pk[34], pk[35]};
+    else return DepthPlane{pk + kPacketHeader, 1};
+}
+
 // One 8^3 block per workgroup pass, the voxels stay in registers while the cameras
 // that see the block are applied in camera order (the running average is order
 // dependent): 4 KiB in, 4 KiB out per block whatever the number of cameras.
@@ -168,28 +176,17 @@ __device__ __forceinline__ void integrate_block_multi(const FrameParams &fp, con
                                                       uint32_t seen, int32_t numCams,
                                                       const float *__restrict__ packets, size_t packetStride)
 {
-    const int lin = 2 * (int)threadIdx.x;
-    const int tx = lin & 7, ty = (lin >> 3) & 7, tz = lin >> 6;
-    const int bx = (int)((uint32_t)e.pos[0] * 8u) + tx;
-    const int by = (int)((uint32_t)e.pos[1] * 8u) + ty;
-    const int bz = (int)((uint32_t)e.pos[2] * 8u) + tz;
-    float4 *cell = reinterpret_cast<float4 *>(dp.blocks + (size_t)e.ptr + lin);
-    float4 v = *cell;
+    const LaneCell lc = lane_cell(dp, e);            // (vh_integrate.hip: the lane's two voxels of the block)
+    float4 v = *lc.cell;
     bool dirty = false;
     for (int c = 0; c < numCams; ++c) {
         if (!((seen >> c) & 1u)) continue;
         const float *pk = packets + packetStride * c;
-        if constexpr (kSensor) {
-            const DepthSensor src{reinterpret_cast<const uint16_t *>(pk + kPacketHeaderU16), pk[32], pk[33], pk[34], pk[35]};
-            dirty |= tsdf_update(fp, pk + 16, src, bx, by, bz, v.x, v.y);
-            dirty |= tsdf_update(fp, pk + 16, src, bx + 1, by, bz, v.z, v.w);
-        } else {
-            const DepthPlane src{pk + kPacketHeader, 1};
-            dirty |= tsdf_update(fp, pk + 16, src, bx, by, bz, v.x, v.y);
-            dirty |= tsdf_update(fp, pk + 16, src, bx + 1, by, bz, v.z, v.w);
-        }
+        const auto src = packet_depth<kSensor>(pk);
+        dirty |= tsdf_update(fp, pk + 16, src, lc.bx, lc.by, lc.bz, v.x, v.y);
+        dirty |= tsdf_update(fp, pk + 16, src, lc.bx + 1, lc.by, lc.bz, v.z, v.w);
     }
-    if (dirty) *cell = v;
+    if (dirty) *lc.cell = v;
 }
 
 template <bool kSensor>
