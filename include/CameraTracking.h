@@ -46,6 +46,11 @@ public:
     void Align(vh_float4 *d_input, vh_float4 *d_inputNormals, vh_float4 *d_target, vh_float4 *d_targetNormals,
                const uint16_t *d_depthInput, const uint16_t *d_depthTarget);
     float4x4 getTransform() { return deltaTransform; }
+    /* Tracking against the model itself (vh_sdf_align, voxelhash.h "tracking against the model itself"): no target maps, no
+     * raycast.  pose: in, the camera -> world start (e.g. the pose of the frame before); out, the result.  Up to `rounds`
+     * rounds with this tracker's distance threshold; the table must use this tracker's stream.  For models fused with a
+     * truncation of a few voxels.  Returns the rounds that took a step; lastError() is the summed residual.  Synchronises. */
+    int AlignToModel(SDF_Hashtable &table, const vh_float4 *d_input, float4x4 &pose, int rounds = 10);
     float lastError() const { return globalCorrespondenceError; }
 };
 

@@ -279,3 +279,15 @@ void CameraTracking::Align(vh_float4 *d_input, vh_float4 *, vh_float4 *d_target,
                        deltaTransform.entries, &last, &rounds), "Align");
     globalCorrespondenceError = (float)last.error;
 }
+
+int CameraTracking::AlignToModel(SDF_Hashtable &table, const vh_float4 *d_input, float4x4 &pose, int rounds)
+{
+    vh_icp_system last;
+    int steps = 0;
+    double T[16];
+    for (int i = 0; i < 16; ++i) T[i] = (double)pose.entries[i];
+    check(vh_sdf_align(table.context(), icp_, d_input, distThres_, rounds, T, &last, &steps), "AlignToModel");
+    for (int i = 0; i < 16; ++i) pose.entries[i] = (float)T[i];
+    globalCorrespondenceError = (float)last.error;
+    return steps;
+}

@@ -571,4 +571,5 @@ static int ensure_candidates(vh_context *c, size_t need)
 #include "vh_api_deintegrate.hip"
 #include "vh_api_dropin.hip"
 #include "vh_api_icp.hip"
+#include "vh_api_track.hip"
 #include "vh_api_dist.hip"

@@ -383,6 +383,26 @@ __device__ __forceinline__ bool icp_step_from_sums(const float *total, double T[
     return icp_step_matrix_d(JTJ, JTr, T);
 }
 
+// The end of a one-launch round, for the workgroup that drew the last ticket: the records added (icp_sum_records), the sums
+// left in the state and, when `solve` is set, lane 0 solves the 6x6 system in double and advances the estimate there.  The
+// stop conditions: summed residual exactly 0 (CameraTracking.cpp:52) and a singular system.  Shared by icp_round_kernel and
+// sdf_round_kernel (vh_track.hip).
+__device__ __forceinline__ void icp_close_round(const float *__restrict__ partials, IcpState *__restrict__ state, const int solve,
+                                                float (*sm)[kIcpStride], float *total)
+{
+    icp_sum_records(partials, (int)gridDim.x, sm, total);
+    if (threadIdx.x < kIcpStride) state->sums[threadIdx.x] = total[threadIdx.x];
+    if (threadIdx.x != 0) return;
+    state->ticket = 0;
+    state->rounds += 1;
+    if (!solve) return;
+    if (total[27] == 0.0f) { state->done = 1; return; }                 // CameraTracking.cpp:52
+    double T[16];
+    for (int i = 0; i < 16; ++i) T[i] = state->T[i];
+    if (!icp_step_from_sums(total, T)) { state->done = 1; state->singular = 1; return; }
+    for (int i = 0; i < 16; ++i) { state->T[i] = T[i]; state->delta[i] = (float)T[i]; }
+}
+
 // One launch per round.  256-lane workgroups (one per compute unit) stride over the pixels and keep the 29 terms in
 // registers; every workgroup stores one partial record (icp_store_record); the last one to finish adds the records
 // (icp_sum_records) and, when `solve` is set, its lane 0 solves the 6x6 system in double and advances the estimate in the
@@ -455,17 +475,7 @@ __global__ __launch_bounds__(kIcpThreads) void icp_round_kernel(IcpParams ip, co
         }
     }
     if (icp_store_record(acc, sums, &drawn, partials, &state->ticket) != (int)gridDim.x - 1) return;
-    icp_sum_records(partials, (int)gridDim.x, sm, total);
-    if (threadIdx.x < kIcpStride) state->sums[threadIdx.x] = total[threadIdx.x];
-    if (threadIdx.x != 0) return;
-    state->ticket = 0;
-    state->rounds += 1;
-    if (!solve) return;
-    if (total[27] == 0.0f) { state->done = 1; return; }                 // CameraTracking.cpp:52
-    double T[16];
-    for (int i = 0; i < 16; ++i) T[i] = state->T[i];
-    if (!icp_step_from_sums(total, T)) { state->done = 1; state->singular = 1; return; }
-    for (int i = 0; i < 16; ++i) { state->T[i] = T[i]; state->delta[i] = (float)T[i]; }
+    icp_close_round(partials, state, solve, sm, total);
 }
 
 // ---- All rounds of an Align in ONE launch (vh_icp_align).  The chain of one-launch rounds pays per round a launch gap and

@@ -25,6 +25,8 @@
 //                      dense boxes of the voxel lattice (one workgroup pass per brick; no counterpart in the reference)
 //   vh_rays.hip        the DDA raycast for arbitrary ray batches: one ray per lane through vh_raycast.hip's per-lane walk
 //                      (no counterpart in the reference)
+//   vh_track.hip       point-to-SDF camera tracking: the ICP's round with the trilinear sample of the model as residual and
+//                      its gradient as normal (no counterpart in the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -49,3 +51,4 @@
 #include "vh_mesh.hip"
 #include "vh_sample.hip"
 #include "vh_rays.hip"
+#include "vh_track.hip"

@@ -70,6 +70,77 @@ __device__ __forceinline__ int sample_resolve(const FrameParams &fp, const DevPt
     return __shfl(p, runs.head);
 }
 
+// The VH_SAMPLE_TRILINEAR sample at u = p / voxelSize (inDomain: |u| < 2^30 on every axis), stated once for sample_points_kernel
+// and sdf_round_kernel (vh_track.hip).  Called by every lane of the wave, with or without a point (inDomain false): the lanes
+// of a run share the look-ups, a point resolves the 1, 2, 4 or 8 distinct blocks of its cell only, and the two corners of
+// an x-edge inside a block are one 16-byte load.  No sample: {NaN, 0, NaN}.
+struct SampleTrilinear { float sdf, weight, g[3]; };
+
+__device__ __forceinline__ SampleTrilinear sample_trilinear(const FrameParams &fp, const DevPtrs &dp, int lane, const float u[3],
+                                                            bool inDomain)
+{
+    const float nan = __builtin_nanf("");
+    SampleTrilinear r = {nan, 0.0f, {nan, nan, nan}};
+    int i[3] = {0, 0, 0};
+    float t[3] = {0.0f, 0.0f, 0.0f};
+    if (inDomain) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float f = __builtin_floorf(u[a]);
+            i[a] = f2i_rz(f);
+            t[a] = u[a] - f;
+        }
+    }
+    const int kx = i[0] >> 3, ky = i[1] >> 3, kz = i[2] >> 3;
+    // which axes the cell crosses a block face on: corner c lies in block (key + (c & cross))
+    const int cross = ((i[0] & 7) == 7 ? 1 : 0) | ((i[1] & 7) == 7 ? 2 : 0) | ((i[2] & 7) == 7 ? 4 : 0);
+    const SampleRuns runs = sample_runs(lane, kx, ky, kz);
+    int ptr[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        // 1, 2, 4 or 8 distinct blocks: a corner whose bits all cross is a block of its own, any other shares the block of
+        // the corner without one of its non-crossing bits (resolved before it)
+        const int p = sample_resolve(fp, dp, lane, runs, inDomain && (c & ~cross) == 0, kx + (c & 1), ky + ((c >> 1) & 1),
+                                     kz + (c >> 2));
+        if ((c & ~cross) == 0) ptr[c] = p;
+        else if (c & ~cross & 1) ptr[c] = ptr[c & 6];
+        else if (c & ~cross & 2) ptr[c] = ptr[c & 5];
+        else ptr[c] = ptr[c & 3];
+    }
+    SampleVoxel v[8];
+#pragma unroll
+    for (int c = 0; c < 8; c += 2) {
+        const int index = sample_index(i[0], i[1] + ((c >> 1) & 1), i[2] + (c >> 2));
+        if (!(cross & 1)) {
+            v[c] = v[c + 1] = SampleVoxel{nan, 0.0f};
+            if (ptr[c] != VH_FREE_BLOCK) {
+                const VoxelPair pair = *reinterpret_cast<const VoxelPair *>(dp.blocks + (size_t)ptr[c] + (size_t)index);
+                v[c] = sample_judge(pair.s0, pair.w0);
+                v[c + 1] = sample_judge(pair.s1, pair.w1);
+            }
+        } else {
+            v[c] = sample_voxel(dp, ptr[c], index);
+            v[c + 1] = sample_voxel(dp, ptr[c + 1], sample_index(i[0] + 1, i[1] + ((c >> 1) & 1), i[2] + (c >> 2)));
+        }
+    }
+    bool all = inDomain;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) all = all && v[c].sdf == v[c].sdf;
+    if (all) {
+        const float tx = t[0], ty = t[1], tz = t[2];
+        const float s0 = v[0].sdf, s1 = v[1].sdf, s2 = v[2].sdf, s3 = v[3].sdf, s4 = v[4].sdf, s5 = v[5].sdf, s6 = v[6].sdf,
+                    s7 = v[7].sdf;
+        r.sdf = sample_lerp(sample_lerp(sample_lerp(s0, s1, tx), sample_lerp(s2, s3, tx), ty),
+                            sample_lerp(sample_lerp(s4, s5, tx), sample_lerp(s6, s7, tx), ty), tz);
+        r.weight = sample_lerp(sample_lerp(sample_lerp(v[0].weight, v[1].weight, tx), sample_lerp(v[2].weight, v[3].weight, tx), ty),
+                               sample_lerp(sample_lerp(v[4].weight, v[5].weight, tx), sample_lerp(v[6].weight, v[7].weight, tx), ty), tz);
+        r.g[0] = sample_lerp(sample_lerp(s1 - s0, s3 - s2, ty), sample_lerp(s5 - s4, s7 - s6, ty), tz) / fp.voxelSize;
+        r.g[1] = sample_lerp(sample_lerp(s2 - s0, s3 - s1, tx), sample_lerp(s6 - s4, s7 - s5, tx), tz) / fp.voxelSize;
+        r.g[2] = sample_lerp(sample_lerp(s4 - s0, s5 - s1, tx), sample_lerp(s6 - s2, s7 - s3, tx), ty) / fp.voxelSize;
+    }
+    return r;
+}
+
 __global__ __launch_bounds__(256) void sample_points_kernel(const FrameParams fp, const DevPtrs dp, int mode, uint32_t n,
                                                             const float *__restrict__ points, float *__restrict__ sdfOut,
                                                             float *__restrict__ weightOut, float *__restrict__ gradOut)
@@ -128,63 +199,11 @@ __global__ __launch_bounds__(256) void sample_points_kernel(const FrameParams fp
             if (!ok) g[0] = g[1] = g[2] = nan;
         }
     } else {
-        int i[3] = {0, 0, 0};
-        float t[3] = {0.0f, 0.0f, 0.0f};
-        if (inDomain) {
+        const SampleTrilinear r = sample_trilinear(fp, dp, lane, u, inDomain);
+        sdf = r.sdf;
+        weight = r.weight;
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float f = __builtin_floorf(u[a]);
-                i[a] = f2i_rz(f);
-                t[a] = u[a] - f;
-            }
-        }
-        const int kx = i[0] >> 3, ky = i[1] >> 3, kz = i[2] >> 3;
-        // which axes the cell crosses a block face on: corner c lies in block (key + (c & cross))
-        const int cross = ((i[0] & 7) == 7 ? 1 : 0) | ((i[1] & 7) == 7 ? 2 : 0) | ((i[2] & 7) == 7 ? 4 : 0);
-        const SampleRuns runs = sample_runs(lane, kx, ky, kz);
-        int ptr[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            // 1, 2, 4 or 8 distinct blocks: a corner whose bits all cross is a block of its own, any other shares the block of
-            // the corner without one of its non-crossing bits (resolved before it)
-            const int p = sample_resolve(fp, dp, lane, runs, inDomain && (c & ~cross) == 0, kx + (c & 1), ky + ((c >> 1) & 1),
-                                         kz + (c >> 2));
-            if ((c & ~cross) == 0) ptr[c] = p;
-            else if (c & ~cross & 1) ptr[c] = ptr[c & 6];
-            else if (c & ~cross & 2) ptr[c] = ptr[c & 5];
-            else ptr[c] = ptr[c & 3];
-        }
-        SampleVoxel v[8];
-#pragma unroll
-        for (int c = 0; c < 8; c += 2) {
-            const int index = sample_index(i[0], i[1] + ((c >> 1) & 1), i[2] + (c >> 2));
-            if (!(cross & 1)) {
-                v[c] = v[c + 1] = SampleVoxel{nan, 0.0f};
-                if (ptr[c] != VH_FREE_BLOCK) {
-                    const VoxelPair pair = *reinterpret_cast<const VoxelPair *>(dp.blocks + (size_t)ptr[c] + (size_t)index);
-                    v[c] = sample_judge(pair.s0, pair.w0);
-                    v[c + 1] = sample_judge(pair.s1, pair.w1);
-                }
-            } else {
-                v[c] = sample_voxel(dp, ptr[c], index);
-                v[c + 1] = sample_voxel(dp, ptr[c + 1], sample_index(i[0] + 1, i[1] + ((c >> 1) & 1), i[2] + (c >> 2)));
-            }
-        }
-        bool all = inDomain;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) all = all && v[c].sdf == v[c].sdf;
-        if (all) {
-            const float tx = t[0], ty = t[1], tz = t[2];
-            const float s0 = v[0].sdf, s1 = v[1].sdf, s2 = v[2].sdf, s3 = v[3].sdf, s4 = v[4].sdf, s5 = v[5].sdf, s6 = v[6].sdf,
-                        s7 = v[7].sdf;
-            sdf = sample_lerp(sample_lerp(sample_lerp(s0, s1, tx), sample_lerp(s2, s3, tx), ty),
-                              sample_lerp(sample_lerp(s4, s5, tx), sample_lerp(s6, s7, tx), ty), tz);
-            weight = sample_lerp(sample_lerp(sample_lerp(v[0].weight, v[1].weight, tx), sample_lerp(v[2].weight, v[3].weight, tx), ty),
-                                 sample_lerp(sample_lerp(v[4].weight, v[5].weight, tx), sample_lerp(v[6].weight, v[7].weight, tx), ty), tz);
-            g[0] = sample_lerp(sample_lerp(s1 - s0, s3 - s2, ty), sample_lerp(s5 - s4, s7 - s6, ty), tz) / fp.voxelSize;
-            g[1] = sample_lerp(sample_lerp(s2 - s0, s3 - s1, tx), sample_lerp(s6 - s4, s7 - s5, tx), tz) / fp.voxelSize;
-            g[2] = sample_lerp(sample_lerp(s4 - s0, s5 - s1, tx), sample_lerp(s6 - s2, s7 - s3, tx), ty) / fp.voxelSize;
-        }
+        for (int a = 0; a < 3; ++a) g[a] = r.g[a];
     }
     if (!have) return;
     sdfOut[at] = sdf;

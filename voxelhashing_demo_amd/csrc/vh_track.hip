@@ -1,0 +1,87 @@
+// vh_track.hip -- point-to-SDF camera tracking: vh_sdf_align, vh_sdf_build_system, vh_sdf_residuals (the
+// rule: include/voxelhash.h, "tracking against the model itself", and tests/sdf_track_ref.py).  No counterpart in the
+// reference: the rule is Bylow et al., "Real-Time Camera Tracking and 3D Reconstruction Using Signed Distance Functions",
+// RSS 2013.
+// Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after vh_sample.hip and vh_icp.hip.
+//
+// A round is the ICP's round (icp_round_kernel) with the model's own distance field where the ICP has a rendered target:
+// every input point is moved by the running camera -> world estimate, the trilinear sample there (sample_trilinear, the
+// sample of vh_sample_sdf) is the residual and its gradient the normal, J = [g, q x g].  Nothing is rendered and nothing is
+// projected.  The 29 sums, their fixed-order reduction, the ticket hand-off and the solve in the last workgroup are
+// vh_icp.hip's functions, called.
+#pragma once
+
+namespace vh {
+
+struct SdfTrackParams {
+    float T[12];         // rows 0..2 of the camera -> world estimate (step API; Align takes them from state->delta)
+    float distThres;
+    int32_t npix;
+};
+
+// One launch per round on the grid vh_icp_create chose.  The look-ups of sample_trilinear are shared across the lanes of a
+// wave, so every lane runs every pass: the trip count is the same for the whole grid, a lane beyond the image takes part
+// without a point, and nothing returns before the last sample.
+//   useState: take the estimate from state->delta (Align) instead of tp.T (step API)
+//   points / sdf / gradient (kWriteMaps): per pixel q (0, 0, 0 where the pixel has no point), the residual (NaN where the
+//   pixel is not kept) and the gradient (0, 0, 0 where it is not kept)
+template <bool kWriteMaps>
+__global__ __launch_bounds__(kIcpThreads) void sdf_round_kernel(const FrameParams fp, const DevPtrs dp, SdfTrackParams tp,
+                                                                const float4 *__restrict__ input, float *__restrict__ partials,
+                                                                float *__restrict__ points, float *__restrict__ sdfOut,
+                                                                float *__restrict__ gradOut, IcpState *__restrict__ state,
+                                                                int useState, int solve)
+{
+    __shared__ float4 sums4[kIcpSumFloats / 4];
+    __shared__ float sm[8][kIcpStride];
+    __shared__ float total[kIcpStride];
+    __shared__ int drawn;
+    float *sums = reinterpret_cast<float *>(sums4);
+    if (useState) {
+        if (state->done) return;                    // (the whole grid)
+#pragma unroll
+        for (int i = 0; i < 12; ++i) tp.T[i] = state->delta[i];
+    }
+    float acc[kIcpTerms];
+#pragma unroll
+    for (int k = 0; k < kIcpTerms; ++k) acc[k] = 0.0f;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int stride = gridDim.x * kIcpThreads;
+    const int passes = (tp.npix + stride - 1) / stride;
+    const float nan = __builtin_nanf("");
+    for (int pass = 0; pass < passes; ++pass) {
+        const int idx = pass * stride + blockIdx.x * kIcpThreads + threadIdx.x;
+        const bool inImage = idx < tp.npix;
+        const float4 p = inImage ? input[idx] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const bool have = p.z != 0.0f;              // the ICP's rule (icp_project)
+        float q[3] = {0.0f, 0.0f, 0.0f}, u[3] = {nan, nan, nan};
+        if (have) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                q[r] = ((tp.T[4 * r + 0] * p.x + tp.T[4 * r + 1] * p.y) + tp.T[4 * r + 2] * p.z) + tp.T[4 * r + 3];
+                u[r] = q[r] / fp.voxelSize;
+            }
+        }
+        const bool inDomain = __builtin_fabsf(u[0]) < kSampleDomain && __builtin_fabsf(u[1]) < kSampleDomain &&
+                              __builtin_fabsf(u[2]) < kSampleDomain;      // false for NaN
+        const SampleTrilinear s = sample_trilinear(fp, dp, lane, u, inDomain);
+        // no sample: s.sdf is NaN and the comparison false
+        const bool kept = __builtin_fabsf(s.sdf) < tp.distThres && __builtin_isfinite(s.g[0]) && __builtin_isfinite(s.g[1]) &&
+                          __builtin_isfinite(s.g[2]);
+        if (kept) icp_accumulate(acc, make_float4(q[0], q[1], q[2], 1.0f), make_float4(s.g[0], s.g[1], s.g[2], 0.0f), s.sdf);
+        if constexpr (kWriteMaps) {
+            if (inImage) {
+                sdfOut[idx] = kept ? s.sdf : nan;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    points[(size_t)idx * 3u + a] = q[a];
+                    gradOut[(size_t)idx * 3u + a] = kept ? s.g[a] : 0.0f;
+                }
+            }
+        }
+    }
+    if (icp_store_record(acc, sums, &drawn, partials, &state->ticket) != (int)gridDim.x - 1) return;
+    icp_close_round(partials, state, solve, sm, total);
+}
+
+}  // namespace vh

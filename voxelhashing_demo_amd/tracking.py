@@ -190,3 +190,120 @@ class FusionLoop:
 
     def close(self):
         self.trk.close()
+
+
+SDF_MAX_ITERS = 10
+
+
+class SdfTracking:
+    """Point-to-SDF alignment against the table's own distance field (vh_sdf_*: no raycast, no projective pairing).
+    SdfTracking(table); Align(input, start_pose) -> the camera -> world pose.  `K` is not needed by the rule and only kept.
+    For models fused with a truncation of a few voxels (include/voxelhash.h, "tracking against the model itself")."""
+
+    def __init__(self, table, K=None, dist_thres: float = DIST_THRES, max_iters: int = SDF_MAX_ITERS, width=None, height=None,
+                 stream=None):
+        self._lib = L.load()
+        self.table = table
+        self.width, self.height = width or table.width, height or table.height
+        self.K = None if K is None else np.ascontiguousarray(np.asarray(K, np.float32).reshape(9))
+        self.dist_thres, self.max_iters = dist_thres, max_iters
+        h = C.c_void_p()
+        L.check(self._lib.vh_icp_create(self.width, self.height, -1, C.byref(h)), "vh_icp_create")
+        self._h = h
+        # the workspace must be bound to the table's stream: the table's own unless the caller names one
+        self.stream_handle = table.stream_handle if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        L.check(self._lib.vh_icp_set_stream(self._h, C.c_void_p(self.stream_handle)), "vh_icp_set_stream")
+        self.pose = np.eye(4)
+        self.last = None
+        self.iterations = 0
+
+    def close(self):
+        if self._h:
+            self._lib.vh_icp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def build_system(self, inp, pose):
+        p = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        sys = L.IcpSystem()
+        L.check(self._lib.vh_sdf_build_system(self.table._h, self._h, _ptr(inp), _fp(p), self.dist_thres, C.byref(sys)),
+                "vh_sdf_build_system")
+        return system_arrays(sys)
+
+    def residuals(self, inp, pose, points, sdf, gradient):
+        """The system, and per pixel the moved point [H, W, 3], the residual [H, W] and the gradient [H, W, 3] (in place)."""
+        p = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        sys = L.IcpSystem()
+        L.check(self._lib.vh_sdf_residuals(self.table._h, self._h, _ptr(inp), _fp(p), self.dist_thres, _ptr(points), _ptr(sdf),
+                                           _ptr(gradient), C.byref(sys)), "vh_sdf_residuals")
+        return system_arrays(sys)
+
+    def Align(self, inp, start_pose):
+        """Up to max_iters rounds from `start_pose` (e.g. the pose of the frame before); the result is kept in `pose`."""
+        p = np.ascontiguousarray(np.asarray(start_pose, np.float64).reshape(16)).copy()
+        sys, it = L.IcpSystem(), C.c_int32()
+        L.check(self._lib.vh_sdf_align(self.table._h, self._h, _ptr(inp), self.dist_thres, self.max_iters, _dp(p), C.byref(sys),
+                                       C.byref(it)), "vh_sdf_align")
+        self.pose, self.last, self.iterations = p.reshape(4, 4), system_arrays(sys), int(it.value)
+        return self.pose
+
+
+class SdfFusionLoop:
+    """The closed loop without a raycast: per uint16 sensor frame
+
+        vh_preprocess(depth)              -> input vertex map
+        vh_sdf_align(input, start = pose) -> pose          (against the model as fused so far)
+        vh_integrate_depth(pose, depth)   -> the model takes the frame
+
+    all on the table's stream; the one host synchronisation of a frame is vh_sdf_align's.  The first frame is integrated at
+    `start_pose`."""
+
+    def __init__(self, table, k_inv, K=None, stream=None, dist_thres: float = DIST_THRES, max_iters: int = SDF_MAX_ITERS):
+        import torch
+        self.table, self.W, self.H = table, table.width, table.height
+        self.k_inv = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        self.trk = SdfTracking(table, K, dist_thres=dist_thres, max_iters=max_iters, stream=stream)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.in_v, self.in_n = (torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev) for _ in range(2))
+        self.stream = self.trk.stream_handle
+        self.pose = None
+        self.frames = 0
+
+    def start(self, depth_u16, start_pose):
+        self.pose = np.asarray(start_pose, np.float64).reshape(4, 4).copy()
+        self.table.integrate_depth(self.pose.astype(np.float32), depth_u16, self.k_inv)
+        self.frames = 1
+        return self.pose
+
+    def track(self, depth_u16):
+        """pre-process + Align only: the new pose (not yet integrated)."""
+        from .hashtable import preprocess
+        preprocess(depth_u16, self.k_inv, self.in_v, self.in_n, stream=self.stream)
+        self.pose = self.trk.Align(self.in_v, self.pose)
+        return self.pose
+
+    def fuse(self, depth_u16):
+        """integrate at the current pose."""
+        self.table.integrate_depth(self.pose.astype(np.float32), depth_u16, self.k_inv)
+        self.frames += 1
+
+    def step(self, depth_u16):
+        """track + fuse in one library call (vh_fusion_step_sdf)."""
+        sys, it = L.IcpSystem(), C.c_int32()
+        trk = self.trk
+        pose = np.ascontiguousarray(self.pose, np.float64).copy()
+        L.check(trk._lib.vh_fusion_step_sdf(self.table._h, trk._h, _ptr(depth_u16), _fp(self.k_inv), trk.dist_thres, trk.max_iters,
+                                            _ptr(self.in_v), _ptr(self.in_n), _dp(pose.reshape(16)), C.byref(sys), C.byref(it)),
+                "vh_fusion_step_sdf")
+        self.pose = trk.pose = pose
+        trk.last, trk.iterations = system_arrays(sys), int(it.value)
+        self.frames += 1
+        return self.pose
+
+    def close(self):
+        self.trk.close()
