@@ -382,6 +382,63 @@ def entries_as_set_(entries):
     return set(map(tuple, np.asarray(entries["pos"]).reshape(-1, 3).tolist()))
 
 
+@pytest.mark.parametrize("mode", [1, 2, 0])
+def test_heap_shortage_refuses_whole_multi_camera_frames(oracle, vh, torch_cuda, mode):
+    """The multi-camera counterpart of test_gpu_pipeline.py::test_heap_shortage_refuses_whole_frames: a one-launch
+    multi-camera frame (pipeline_shards 1 and 2) whose new blocks outnumber the free blocks inserts none of them -- every
+    winner counts as heap_exhausted, frame after frame, and the table stays consistent; two launches per frame
+    (pipeline_shards 0) serve as many winners as the heap has blocks."""
+    torch = torch_cuda
+    w, h, nb = 64, 48, 1 << 10
+    prims = synth.room_primitives()
+    loop = synth.camera_loop(60, phase=vdist.camera_phase(0, 1))
+    p0, p5 = loop[0], loop[5]
+    v0, v5 = (synth.render_room_verts(p, w, h, prims).numpy() for p in (p0, p5))
+    probe = oracle.OracleTable(oracle.default_params(numBuckets=nb, numVoxelBlocks=4096), w, h, 1)
+    probe.integrate(p0, v0)
+    n0 = len(probe.allocated())                            # blocks the frame at pose 0 inserts
+    probe.integrate(p5, v5)
+    more = len(probe.allocated()) - n0                     # ... and a frame at pose 5 would
+    assert n0 > 100 and more > 10
+    kw = dict(numBuckets=nb, numVoxelBlocks=n0 + 3)
+    plan = vdist.ShardPlan(nb, 1)
+    sh = vdist.HipShard(vh.default_params(**kw), w, h, 1, plan, 0, w * h // 2, batch=3)
+    sh.table.set_option("pipeline_shards", mode)
+    full = oracle.OracleTable(oracle.default_params(**kw), w, h, 1)
+    keep = []                # (pipeline_shards 2: a batch's buffers stay valid until its last frame's half has run)
+
+    def feed(batch, pose, verts):
+        sub = vdist.HipShard.__new__(vdist.HipShard)       # (the shard's buffers are sized for 3 frames: a dense prefix)
+        sub.__dict__.update(sh.__dict__)
+        sub.batch = batch
+        sub.bins_send, sub.bins_recv = sh.bins_send[:, :batch].contiguous(), sh.bins_recv[:, :batch].contiguous()
+        sub.packet, sub.packets = sh.packet[:batch].contiguous(), sh.packets[:, :batch].contiguous()
+        dv = [torch.from_numpy(verts).cuda() for _ in range(batch)]
+        keep.append((sub, dv))
+        vdist.loopback_step([sub], [[pose] * batch], [dv])
+
+    feed(1, p0, v0)                                        # n0 new blocks, n0 + 3 free: served
+    full.integrate(p0, v0)
+    assert check_shard_against_full(sh.table, full, 0, nb, 5) == n0
+    feed(3, p5, v5)                                        # `more` wanted, 3 free
+    sh.table.synchronize()
+    c = sh.table.counters()
+    tab = sh.table.hash_table()
+    alloc = tab[tab["ptr"] != -1]
+    if mode == 0:
+        assert len(alloc) == n0 + 3
+    else:
+        print(f"mode {mode}: allocated {len(alloc)} (n0 {n0}), heap_counter {c['heap_counter']}, "
+              f"heap_exhausted {c['heap_exhausted']} (more {more})")
+        assert len(alloc) == n0 and c["heap_counter"] == 2 and c["heap_exhausted"] == 3 * more
+        assert entries_as_set_(alloc) == entries_as_set_(full.allocated())
+    assert len(entries_as_set_(alloc)) == len(alloc) and len(set(alloc["ptr"].tolist())) == len(alloc)
+    for b in range(0, len(tab), 5):                        # entries still form a prefix of every bucket
+        live = tab["ptr"][b:b + 5] != -1
+        assert not np.any(live[1:] & ~live[:-1])
+    sh.table.close()
+
+
 def test_one_launch_multi_camera_frames_across_the_epoch_wrap(oracle, vh, torch_cuda):
     """The claim words carry a 9-bit lock epoch; at the wrap they are cleared -- which the frame whose deferred half is
     still pending must not see: 1 040 multi-camera frames (one shard, batches of 8) straddle the wraps at frames 511 and 1 022."""

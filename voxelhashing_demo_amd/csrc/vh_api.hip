@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -91,11 +92,20 @@ struct TimedLaunch {
     hipEvent_t start, stop;
 };
 
-struct MultiPending {
-    bool active = false;
-    uint32_t epochOld = 0;
-    int32_t doneTag = 0;                   // what that frame's commit phase publishes (overflow list)
-    const float *packetsOld = nullptr;     // the caller's packets of that frame: valid until the half has been launched
+// The frame whose second half (commit + TSDF update) is still to be launched: at most one, of either kind -- every entry point
+// that starts a frame of one kind flushes the other (vh_integrate / vh_integrate_depth the multi-camera half,
+// vh_apply_frames_batch the single-camera one).  The buffer parity and counter set it used (vh_context: pipeParity, pipeSet) are
+// shared by the two pipelines and outlive it.
+struct PendingFrame {
+    enum Kind { kNone, kSingle, kMulti } kind = kNone;
+    int32_t doneTag = 0;                   // its tag (lock epochs since creation): what its commit phase publishes (overflow list)
+    // a single-camera frame (vh_api_frame.hip: launch_pipelined)
+    FrameParams fp;                        // that frame's parameters
+    int sensor = 0;                        // its private depth copy: 0 = float camera-z plane, 1 = uint16 sensor image
+    float k[4] = {0, 0, 0, 0};             // K_inv row 2 and the depth unit of a sensor frame
+    // a multi-camera frame (vh_api_shard.hip: launch_multi_pipelined)
+    uint32_t epoch = 0;
+    const float *packets = nullptr;        // the caller's packets of that frame: valid until the half has been launched
     size_t packetStride = 0;
     int32_t numCams = 0;
     int packetFormat = 0;
@@ -178,13 +188,9 @@ struct vh_context {
     DevBuf<float> fusedPlane;      // packed camera-z plane launch 1 of the two-launch frame leaves for launch 2 (large images)
     int pipeline = 0;
     int pipeIntegrateGrid = 512;   // workgroups of the deferred TSDF update inside a pipelined launch
-    bool pipePending = false;      // the commit + TSDF update of the last frame are still to be launched
-    FrameParams pipeFp;            // that frame's parameters
-    int32_t pipeDoneTag = 0;       // ... and its tag (lock epochs since creation): what its commit phase publishes (overflow list)
-    int pipeSet = 0;               // counter set its claim / walk filled
+    PendingFrame pend;             // the frame whose commit + TSDF update have not been launched yet
+    int pipeSet = 0;               // counter set the last pipelined frame's claim / walk filled
     int pipeParity = 0;            // which of the two buffer sets it used
-    int pipeSensor = 0;            // its private depth copy: 0 = float camera-z plane, 1 = uint16 sensor image
-    float pipeK[4] = {0, 0, 0, 0}; // K_inv row 2 and the depth unit of a sensor frame
     unsigned long long *claimBuf[2] = {nullptr, nullptr};
     int4 *candBuf[2] = {nullptr, nullptr};
     VoxelEntry *compactBuf[2] = {nullptr, nullptr};
@@ -198,7 +204,6 @@ struct vh_context {
     bool serialFallback = false;           // a serialised launch has timed out (vh_counters.spin_timeouts): overflow-list frames take two launches from now on
     int debugSkipRoles = 0;                // diagnostics: roles of the pipelined launch that return at once (timing only; the model is wrong)
     int pipelineShards = 1;                // option "pipeline_shards": vh_apply_frames_batch runs a batch of B multi-camera frames as B + 1 launches (1) or B (2: the last frame's half stays pending across calls)
-    MultiPending multiPend;                // the multi-camera frame whose commit + TSDF update have not been launched yet
     void *multiFirstEvent = nullptr;       // hipEvent_t recorded behind the first launch of every vh_apply_frames_batch (vh_dist: the previous batch's packets are free)
     VoxelEntry *compactHome = nullptr;     // the compact buffer of creation: what PtrContainer names, where settle() leaves the dense list
     DevBuf<float> planeBuf[2];
@@ -344,9 +349,10 @@ static void default_projection(vh_context *c)
 }
 
 static int check_spin_timeouts(vh_context *c);  // vh_api_model.hip: behind a host synchronisation, VH_ERR_TIMEOUT if a serialised launch gave up
-static int flush_pending(vh_context *c);       // vh_api_frame.hip: launches a pipelined frame's deferred half
-static int flush_single_pending(vh_context *c);
-static int flush_multi_pending(vh_context *c);     // vh_api_shard.hip: the same for a multi-camera frame (pipeline_shards 2)
+static int flush_pending(vh_context *c);       // vh_api_frame.hip: launches the pending frame's deferred half, of either kind
+static int flush_pending(vh_context *c, PendingFrame::Kind kind);      // ... if it is of that kind
+struct MultiBatch;
+static int launch_multi_pipelined(vh_context *c, const MultiBatch *mb, int b, const GenJob *job = nullptr);      // vh_api_shard.hip
 static int settle(vh_context *c);              // ... and folds a two-ended compact list into the dense one (observers)
 
 static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_context **out)
@@ -489,7 +495,7 @@ extern "C" int vh_destroy(vh_context *c)
 extern "C" int vh_set_stream(vh_context *c, void *stream)
 {
     if (!c) return fail(VH_ERR_INVALID_ARGUMENT, "null context");
-    if (c->pipePending) {            // the deferred half of the last frame belongs on the stream that frame ran on
+    if (c->pend.kind == PendingFrame::kSingle) {            // the deferred half of the last frame belongs on the stream that frame ran on
         DeviceGuard guard(c->device);
         const int rc = flush_pending(c);
         if (rc != VH_OK) return rc;

@@ -89,6 +89,23 @@ static uint32_t walk_blocks(const vh_context *c)
     return (uint32_t)grid_for(c->numEntries, kFlattenThreads * ((c->fp.flags & kFlagWalkShort) ? kEntriesPerLaneShort : kEntriesPerLane));
 }
 
+// ... of the multi-camera walk: the reference's walk with 4 entries per lane from 32 MB of entries on, else 8; the index walk
+// for flatten_variant 4 without the overflow list (holes and chains take the reference's walk)
+static bool multi_walk_indexed(const vh_context *c) { return c->flattenVariant == kWalkIndexed && !(c->fp.flags & kFlagOverflow); }
+static bool multi_walk_short(const vh_context *c) { return c->numEntries * sizeof(VoxelEntry) >= ((size_t)32 << 20); }
+static uint32_t multi_walk_blocks(const vh_context *c)
+{
+    return multi_walk_indexed(c) ? (uint32_t)grid_for(((size_t)c->ownedBuckets + 31) / 32, kFlattenThreads * kIndexWords)
+                                 : (uint32_t)grid_for(c->numEntries, kFlattenThreads * (multi_walk_short(c) ? kEntriesPerLaneShort : kEntriesPerLane));
+}
+
+// 1024-record slices of a key bin of `capacity` records (one claim workgroup each, vh_shard.hip: claim_bin_slice)
+static uint32_t bin_parts(int32_t capacity) { return (uint32_t)std::max(1, grid_for((size_t)capacity, 256 * 4)); }
+
+// a run-time bool as a template argument: f(std::true_type / std::false_type)
+template <class F>
+static int with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
 static int launch_flatten(vh_context *c)
 {
     const dim3 grid(walk_blocks(c));
@@ -245,135 +262,172 @@ static bool serial_launch_pays(const vh_context *c, uint32_t waiters)
     return c->pipelineOverflow == 2 || waiters <= kSerialMaxWaiters;
 }
 
-// can this context run its frames pipelined right now?
+// can this context run one-launch frames (single- or multi-camera) whose claim + walk roles have `waiters` workgroups?
+static bool can_pipeline(const vh_context *c, uint32_t waiters)
+{
+    return c->fp.bucketSize <= kMaxPipelinedBucket && !c->viewBlocks && serial_launch_pays(c, waiters);
+}
+
+// ... its single-camera frames, right now?
 static bool pipeline_applies(const vh_context *c)
 {
     return c->pipeline && c->fusedFrame && (c->flattenVariant == kWalkStridedBallot || c->flattenVariant == kWalkIndexed) &&
-           c->fp.bucketSize <= kMaxPipelinedBucket && !c->viewBlocks && serial_launch_pays(c, host_num_tiles(c) + walk_blocks(c));
+           can_pipeline(c, host_num_tiles(c) + walk_blocks(c));
+}
+
+// What a pipelined launch works on.  Buffers alternate and counter sets rotate from frame to frame -- single- and multi-camera
+// frames alike, across flushes too (a flush leaves the two sets it did not consume empty; at creation all three are).
+struct PipeRotation {
+    int oldParity, newParity;          // buffer sets of the pending frame and of the new one
+    int iNew, iOld, iClear;            // counter sets (0..2): filled by the new frame (c->pipeSet once it is pending), consumed, cleared by this launch
+    DevPtrs dpOld, dpNew;
+};
+// ... and its part of the launch's argument block (PipeArgs / MultiPipeArgs)
+template <class Args>
+static PipeRotation pipe_rotation(const vh_context *c, Args &a, bool hasNew, bool hasOld)
+{
+    PipeRotation r;
+    r.oldParity = c->pipeParity; r.newParity = r.oldParity ^ 1;
+    r.iOld = c->pipeSet; r.iNew = (r.iOld + 1) % 3; r.iClear = (r.iNew + 1) % 3;
+    r.dpNew = pipe_view(c, r.newParity); r.dpOld = pipe_view(c, r.oldParity);
+    a.setNew = kPipeSetStride * r.iNew; a.setOld = kPipeSetStride * r.iOld; a.setClear = kPipeSetStride * r.iClear;
+    a.hasNew = hasNew; a.hasOld = hasOld;
+    a.doneTag = c->pend.doneTag;
+    a.spinLimit = c->spinLimit ? c->spinLimit : kSpinLimitDefault;
+    return r;
+}
+
+// What follows a successful pipelined launch.  kind: of the frame it started (kNone: a flush launch; the caller fills in what that
+// kind keeps).  twoEnded: the consumed frame's list has two ends to fold (single-camera; the multi-camera list is dense).
+static void pipe_launched(vh_context *c, const PipeRotation &r, bool serial, PendingFrame::Kind kind, bool hasOld, bool twoEnded, bool countFrame)
+{
+    if (serial && kind != PendingFrame::kNone && hasOld) c->serialQueued = true;       // (its claim / walk workgroups wait: check_spin_timeouts)
+    if (!twoEnded) c->foldA = -1;
+    else if (hasOld) { const int set = kPipeSetStride * r.iOld; c->foldA = kPipeScan + set; c->foldB = kPipeScanB + set; c->foldNew = kPipeNew + set; }
+    c->pend.kind = kind;               // (kNone: pipeSet / pipeParity stay, the next run starts on the following set)
+    if (kind != PendingFrame::kNone) {
+        c->pend.doneTag = (int32_t)(c->epochTotal & 0x7fffffffu) | 0x40000000;      // (never 0, the counter's initial value)
+        c->pipeSet = r.iNew;
+        c->pipeParity = r.newParity;
+        c->dp.claim = r.dpNew.claim;             // the "current" buffers of everything that is not pipelined
+        c->dp.candidates = r.dpNew.candidates;
+        c->dp.compact = r.dpNew.compact;
+    }
+    c->occupiedCounter = kCompactCount;
+    c->compactArmed = false;
+    if (countFrame && c->profiling) c->profiledFrames += 1;
+}
+
+// The build of frame_pipelined_kernel for this context's state (vh_frame.hip: kLean*): a lean one when there is no overflow list
+// and both frames' option flags, the walk and the claim form are exactly what that build has folded in.
+static int lean_for(const vh_context *c, uint32_t flagsOld, bool band, bool indexed, bool claimPerWave)
+{
+    if (c->fp.flags & kFlagOverflow) return kLeanNone;
+    for (int k = kLeanShort; k < kLeanBuilds; ++k) {
+        const LeanBuild lb = lean_build(k);
+        const bool rayDda = (lb.flags & kFlagBandRayDda) != 0u;
+        if (lb.flags == c->fp.flags && lb.flags == flagsOld && lb.indexed == indexed && lb.claimPerWave == claimPerWave &&
+            (!rayDda || band) && (!lb.indexed || !band))          // (the ray-DDA builds exist with the band only, the walk-free ones without)
+            return k;
+    }
+    return kLeanNone;
+}
+
+// run-time (lean, band, serial) -> the instantiation.  Only the builds named here exist.
+template <int kLean>
+using LeanC = std::integral_constant<int, kLean>;
+template <class In, class Depth, class... Args>
+static int launch_pipelined_build(vh_context *c, int lean, bool band, bool serial, dim3 grid, Args... args)
+{
+    using Yes = std::true_type;
+    using No = std::false_type;
+    auto go = [&](auto leanC, auto bandC, auto serialC) {
+        return launch(c, kPhaseFramePipelined, frame_pipelined_kernel<In, Depth, decltype(bandC)::value, decltype(serialC)::value, decltype(leanC)::value>,
+                      grid, dim3(256), args...);
+    };
+    switch (lean) {
+    case kLeanShort: return with_bool(band, [&](auto b) { return go(LeanC<kLeanShort>{}, b, No{}); });
+    case kLeanShortNt: return with_bool(band, [&](auto b) { return go(LeanC<kLeanShortNt>{}, b, No{}); });
+    case kLeanRayDda: return go(LeanC<kLeanRayDda>{}, Yes{}, No{});
+    case kLeanRayDdaNt: return go(LeanC<kLeanRayDdaNt>{}, Yes{}, No{});
+    case kLeanIndexed: return go(LeanC<kLeanIndexed>{}, No{}, No{});
+    case kLeanIndexedNt: return go(LeanC<kLeanIndexedNt>{}, No{}, No{});
+    case kLeanIndexedWave: return go(LeanC<kLeanIndexedWave>{}, No{}, No{});
+    case kLeanIndexedWaveNt: return go(LeanC<kLeanIndexedWaveNt>{}, No{}, No{});
+    default: return with_bool(band, [&](auto b) { return with_bool(serial, [&](auto q) { return go(LeanC<kLeanNone>{}, b, q); }); });
+    }
 }
 
 // One launch: {claim || walk} of the new frame (in != nullptr) and {commit + integrate} of the pending one.
 template <class In>
 static int launch_pipelined(vh_context *c, const In *in, int newSensor, const float newK[4])
 {
-    const bool hasNew = in != nullptr, hasOld = c->pipePending;
+    const bool hasNew = in != nullptr, hasOld = c->pend.kind == PendingFrame::kSingle;
     if (!hasNew && !hasOld) return VH_OK;
     int rc;
     if (!hasOld && (rc = ensure_pipeline_buffers(c)) != VH_OK) return rc;
-    // buffers alternate and counter sets rotate from frame to frame, across flushes too (a flush leaves
-    // the two sets it did not consume empty; at creation all three are)
-    const int oldParity = c->pipeParity, newParity = oldParity ^ 1;
-    const int setOld = c->pipeSet, setNew = (setOld + 1) % 3;
     PipeArgs a;
+    const PipeRotation r = pipe_rotation(c, a, hasNew, hasOld);
     const bool band = c->fp.allocBand > 0.0f;       // (the new frame's; the pending frame's claims are done)
-    // (without a band a claim workgroup takes four launch tiles, one per wave: claim_tile_wave, vh_alloc.hip)
     a.walkBlocks = hasNew ? walk_blocks(c) : 0u;
     a.walkIndexed = c->flattenVariant == kWalkIndexed ? 1u : 0u;
     const bool serial = (c->fp.flags & kFlagOverflow) != 0u;
-    // the lean builds (vh_frame.hip): no band, no list, the reference's walk, and both frames' option flags exactly the walk's
-    int lean = 0;
-    if (!serial) {                        // (with a band: the ray band only -- kFlagBandDda is a flag like the others)
-        const uint32_t fo = hasOld ? c->pipeFp.flags : c->fp.flags;
-        if (a.walkIndexed) {                // the walk-free frame (flatten_variant 4): builds of its own, without a band
-            if (!band && c->fp.flags == kFlagWalkShort && fo == kFlagWalkShort) lean = 5;
-            else if (!band && c->fp.flags == (kFlagWalkShort | kFlagWalkNt) && fo == (kFlagWalkShort | kFlagWalkNt)) lean = 6;
-        }
-        else if (c->fp.flags == kFlagWalkShort && fo == kFlagWalkShort) lean = 1;
-        else if (c->fp.flags == (kFlagWalkShort | kFlagWalkNt) && fo == (kFlagWalkShort | kFlagWalkNt)) lean = 2;
-        else if (band && c->fp.flags == (kFlagWalkShort | kFlagBandRayDda) && fo == c->fp.flags) lean = 3;
-        else if (band && c->fp.flags == (kFlagWalkShort | kFlagWalkNt | kFlagBandRayDda) && fo == c->fp.flags) lean = 4;
-    }
     // The walk-free frame of a large image: a claim workgroup takes four launch tiles, one per wave (claim_tile_wave, vh_alloc.hip:
     // a quarter of the waves, each with four pixels per lane).  C3 28.4 -> 26.7 us same box; a 640x480 frame prefers the tile per
     // workgroup (8.9 against 11.1 us: the longer chain per wave is its tail), and so does every frame under the reference's walk
-    // (C2 18.9 -> 19.9-22.7 us, C3 72.0 -> 71.5): profiles/r05_claim_wave_tile_ab.txt.  Hence the size rule.
-    a.claimPerWave = (hasNew && (lean == 5 || lean == 6) && host_num_tiles(c) > 2400u) ? 1u : 0u;
-    if (a.claimPerWave) lean += 2;                                // builds 7 / 8
+    // (C2 18.9 -> 19.9-22.7 us, C3 72.0 -> 71.5): profiles/r05_claim_wave_tile_ab.txt.  Hence the size rule (builds 7 / 8).
+    const uint32_t flagsOld = hasOld ? c->pend.fp.flags : c->fp.flags;
+    const bool large = host_num_tiles(c) > 2400u;
+    int lean = lean_for(c, flagsOld, band, a.walkIndexed != 0u, false);
+    a.claimPerWave = (hasNew && large && (lean == kLeanIndexed || lean == kLeanIndexedNt)) ? 1u : 0u;
+    if (a.claimPerWave) lean = lean_for(c, flagsOld, band, true, true);
     a.claimBlocks = !hasNew ? 0u : a.claimPerWave ? (host_num_tiles(c) + 3u) / 4u : host_num_tiles(c);
     a.commitBlocks = hasOld ? (uint32_t)c->commitBlocks : 0u;
     a.integrateBlocks = hasOld ? (uint32_t)c->pipeIntegrateGrid : 0u;
     // (the walk-free frame of a large image: its TSDF update is on the critical path, not under a walk -- twice the workgroups:
     // C3 26.1 -> 25.1 us, while C2 prefers the 512 it has, 8.7 against 9.0)
-    if (hasOld && a.walkIndexed && host_num_tiles(c) > 2400u) a.integrateBlocks *= 2u;
+    if (hasOld && a.walkIndexed && large) a.integrateBlocks *= 2u;
     a.numEntries = (uint32_t)c->numEntries;
-    a.setNew = kPipeSetStride * setNew; a.setOld = kPipeSetStride * setOld; a.setClear = kPipeSetStride * ((setNew + 1) % 3);
-    a.hasNew = hasNew; a.hasOld = hasOld;
     a.claimSpan = claim_span(c, a.claimBlocks, a.walkBlocks);
     a.claimRatio = claim_ratio(a.claimBlocks, a.claimSpan);
-    a.planeNew = (hasNew && !newSensor) ? c->planeBuf[newParity].get() : nullptr;
-    a.rawNew = (hasNew && newSensor) ? c->rawBuf[newParity].get() : nullptr;
+    a.planeNew = (hasNew && !newSensor) ? c->planeBuf[r.newParity].get() : nullptr;
+    a.rawNew = (hasNew && newSensor) ? c->rawBuf[r.newParity].get() : nullptr;
     a.filter = c->claimFilter;
-    a.filtNew = kPendFilterWords * (uint32_t)setNew; a.filtOld = kPendFilterWords * (uint32_t)setOld;
-    a.filtClear = kPendFilterWords * (uint32_t)((setNew + 1) % 3);
-    a.doneTag = c->pipeDoneTag;
-    a.spinLimit = c->spinLimit ? c->spinLimit : kSpinLimitDefault;
+    a.filtNew = kPendFilterWords * (uint32_t)r.iNew; a.filtOld = kPendFilterWords * (uint32_t)r.iOld;
+    a.filtClear = kPendFilterWords * (uint32_t)r.iClear;
 #ifdef VH_DEBUG_SKIP_ROLES
     a.skipRoles = (uint32_t)c->debugSkipRoles;
 #endif
-    const DevPtrs dpNew = pipe_view(c, newParity), dpOld = pipe_view(c, oldParity);
     const dim3 grid(a.commitBlocks + a.integrateBlocks + a.claimBlocks + a.walkBlocks);
     In inNew{};
     if (hasNew) inNew = *in;
-#define VH_LAUNCH_PIPELINED(DEPTH, BAND, SERIAL, LEAN) \
-    launch(c, kPhaseFramePipelined, frame_pipelined_kernel<In, DEPTH, BAND, SERIAL, LEAN>, grid, dim3(256), c->fp, dpNew, inNew, c->pipeFp, dpOld, d, a)
-#define VH_LAUNCH_PIPELINED_ANY(DEPTH) \
-    (lean == 1 ? (band ? VH_LAUNCH_PIPELINED(DEPTH, true, false, 1) : VH_LAUNCH_PIPELINED(DEPTH, false, false, 1)) \
-     : lean == 2 ? (band ? VH_LAUNCH_PIPELINED(DEPTH, true, false, 2) : VH_LAUNCH_PIPELINED(DEPTH, false, false, 2)) \
-     : lean == 3 ? VH_LAUNCH_PIPELINED(DEPTH, true, false, 3) \
-     : lean == 4 ? VH_LAUNCH_PIPELINED(DEPTH, true, false, 4) \
-     : lean == 5 ? VH_LAUNCH_PIPELINED(DEPTH, false, false, 5) \
-     : lean == 6 ? VH_LAUNCH_PIPELINED(DEPTH, false, false, 6) \
-     : lean == 7 ? VH_LAUNCH_PIPELINED(DEPTH, false, false, 7) \
-     : lean == 8 ? VH_LAUNCH_PIPELINED(DEPTH, false, false, 8) \
-     : serial ? (band ? VH_LAUNCH_PIPELINED(DEPTH, true, true, 0) : VH_LAUNCH_PIPELINED(DEPTH, false, true, 0)) \
-              : (band ? VH_LAUNCH_PIPELINED(DEPTH, true, false, 0) : VH_LAUNCH_PIPELINED(DEPTH, false, false, 0)))
-    if (hasOld && c->pipeSensor) {
-        const DepthSensor d{c->rawBuf[oldParity], c->pipeK[0], c->pipeK[1], c->pipeK[2], c->pipeK[3]};
-        rc = VH_LAUNCH_PIPELINED_ANY(DepthSensor);
+    if (hasOld && c->pend.sensor) {
+        const DepthSensor d{c->rawBuf[r.oldParity], c->pend.k[0], c->pend.k[1], c->pend.k[2], c->pend.k[3]};
+        rc = launch_pipelined_build<In, DepthSensor>(c, lean, band, serial, grid, c->fp, r.dpNew, inNew, c->pend.fp, r.dpOld, d, a);
     } else {
-        const DepthPlane d{c->planeBuf[oldParity], 1};
-        rc = VH_LAUNCH_PIPELINED_ANY(DepthPlane);
+        const DepthPlane d{c->planeBuf[r.oldParity], 1};
+        rc = launch_pipelined_build<In, DepthPlane>(c, lean, band, serial, grid, c->fp, r.dpNew, inNew, c->pend.fp, r.dpOld, d, a);
     }
-#undef VH_LAUNCH_PIPELINED_ANY
-#undef VH_LAUNCH_PIPELINED
     if (rc != VH_OK) return rc;
-    if (serial && hasNew && hasOld) c->serialQueued = true;       // (its claim / walk workgroups wait: check_spin_timeouts)
-    if (hasOld) { c->foldA = kPipeScan + a.setOld; c->foldB = kPipeScanB + a.setOld; c->foldNew = kPipeNew + a.setOld; }
+    pipe_launched(c, r, serial, hasNew ? PendingFrame::kSingle : PendingFrame::kNone, hasOld, true, false);     // (run_frame counts the frame)
     if (hasNew) {
-        c->pipePending = true;
-        c->pipeFp = c->fp;
-        c->pipeDoneTag = (int32_t)(c->epochTotal & 0x7fffffffu) | 0x40000000;      // (never 0, the counter's initial value)
-        c->pipeSet = setNew;
-        c->pipeParity = newParity;
-        c->pipeSensor = newSensor;
-        if (newK) std::memcpy(c->pipeK, newK, sizeof c->pipeK);
-        c->dp.claim = dpNew.claim;               // the "current" buffers of everything that is not pipelined
-        c->dp.candidates = dpNew.candidates;
-        c->dp.compact = dpNew.compact;
-    } else {
-        c->pipePending = false;          // (pipeSet / pipeParity stay: the next run starts on the following set)
+        c->pend.fp = c->fp;
+        c->pend.sensor = newSensor;
+        if (newK) std::memcpy(c->pend.k, newK, sizeof c->pend.k);
     }
-    c->occupiedCounter = kCompactCount;
-    c->compactArmed = false;
     return VH_OK;
 }
 
-static int flush_single_pending(vh_context *c)
+// the pending frame's deferred half in a launch of its own, if it is of that kind (every observer comes through flush_pending)
+static int flush_pending(vh_context *c, PendingFrame::Kind kind)
 {
-    if (!c->pipePending) return VH_OK;
-    const int rc = launch_pipelined<VertexMap>(c, nullptr, 0, nullptr);
+    if (c->pend.kind != kind || kind == PendingFrame::kNone) return VH_OK;
+    const int rc = kind == PendingFrame::kSingle ? launch_pipelined<VertexMap>(c, nullptr, 0, nullptr) : launch_multi_pipelined(c, nullptr, 0);
     if (rc != VH_OK) return rc;
     VH_HIP(hipGetLastError());
     return VH_OK;
 }
-
-// (at most one of the two is pending: every entry point that starts a frame of one kind flushes the other --
-// vh_integrate / vh_integrate_depth the multi-camera half, vh_apply_frames_batch the single-camera one)
-static int flush_pending(vh_context *c)
-{
-    const int rc = flush_single_pending(c);
-    return rc != VH_OK ? rc : flush_multi_pending(c);
-}
+static int flush_pending(vh_context *c) { return flush_pending(c, c->pend.kind); }
 
 // For whoever looks at the compact list from outside a frame (download, device pointers, the step-level TSDF
 // update, collection, an explicit flush or synchronisation): the pending half first, then end B of the
@@ -494,7 +548,7 @@ extern "C" int vh_integrate(vh_context *c, const float pose[16], const vh_float4
     DeviceGuard guard(c->device);
     // a single-camera frame on a context that still holds a multi-camera frame's deferred half (pipeline_shards 2, e.g. the
     // shard of a vh_dist): that half is served first -- the two pipelines share buffer parity and counter sets
-    int rc = flush_multi_pending(c);
+    int rc = flush_pending(c, PendingFrame::kMulti);
     if (rc == VH_OK) rc = vh_set_pose(c, pose);
     if (rc == VH_OK) rc = vh_reset_mutexes(c);
     if (rc != VH_OK) return rc;
@@ -510,7 +564,7 @@ extern "C" int vh_integrate_depth(vh_context *c, const float pose[16], const uin
     VH_TRACE("vh_integrate_depth");
     if (!c || !pose || !d_depth || !k_inv) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
     DeviceGuard guard(c->device);
-    int rc = flush_multi_pending(c);                      // (see vh_integrate)
+    int rc = flush_pending(c, PendingFrame::kMulti);      // (see vh_integrate)
     if (rc == VH_OK) rc = vh_set_pose(c, pose);
     if (rc == VH_OK) rc = vh_reset_mutexes(c);
     if (rc != VH_OK) return rc;

@@ -286,7 +286,7 @@ static hipError_t reset_model(vh_context *c)
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     c->fp.epoch = 0;
     c->fusedParity = 0;
-    c->pipePending = false;
+    c->pend.kind = PendingFrame::kNone;
     c->compactArmed = false;
     c->occupiedCounter = kCompactCount;
     c->foldA = -1;
@@ -432,7 +432,7 @@ extern "C" int vh_set_option(vh_context *c, const char *name, int value)
     if (std::strcmp(name, "gen_frames_per_launch") == 0 && value >= 1 && value <= kGenBatch) { c->genFramesPerLaunch = value; return VH_OK; }
     if (std::strcmp(name, "pipeline_shards") == 0) {
         if (value < 0 || value > 2) return fail(VH_ERR_INVALID_ARGUMENT, "pipeline_shards: 0, 1 or 2");
-        if (value < 2) { DeviceGuard g(c->device); const int frc = flush_multi_pending(c); if (frc != VH_OK) return frc; }
+        if (value < 2) { DeviceGuard g(c->device); const int frc = flush_pending(c, PendingFrame::kMulti); if (frc != VH_OK) return frc; }
         c->pipelineShards = value;
         return VH_OK;
     }

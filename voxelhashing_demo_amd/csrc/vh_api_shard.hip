@@ -367,7 +367,7 @@ extern "C" int vh_write_packets_u16_batch(vh_context *c, int32_t batch, const fl
 }
 
 // One launch of the multi-camera pipeline: {claim || walk} of frame b of batch `mb` (null: none) and {commit + TSDF
-// update} of the frame that is pending (c->multiPend), if any.
+// update} of the frame that is pending (c->pend), if any.
 struct MultiBatch {
     const int4 *bins;
     const float *packets;
@@ -376,32 +376,26 @@ struct MultiBatch {
     bool perBatch;           // the bins hold the whole batch (frameStride 0): a launch claims the records of its frame
 };
 
-static int launch_multi_pipelined(vh_context *c, const MultiBatch *mb, int b, const GenJob *job = nullptr)
+static int launch_multi_pipelined(vh_context *c, const MultiBatch *mb, int b, const GenJob *job)
 {
-    MultiPending &mp = c->multiPend;
-    const bool doNew = mb != nullptr, hasOld = mp.active;
+    PendingFrame &pend = c->pend;
+    const bool doNew = mb != nullptr, hasOld = pend.kind == PendingFrame::kMulti;
     if (!doNew && !hasOld) return VH_OK;
     int rc;
     if (doNew && (rc = vh_reset_mutexes(c)) != VH_OK) return rc;
     uint32_t *maskOf[2] = {c->dp.compactMask, c->maskBuf2};
-    const int oldParity = c->pipeParity, newParity = oldParity ^ 1;
-    const int setOld = c->pipeSet, setNew = (setOld + 1) % 3;
     MultiPipeArgs a;
     std::memset(&a, 0, sizeof a);
+    PipeRotation r = pipe_rotation(c, a, doNew, hasOld);
     a.numEntries = (uint32_t)c->numEntries;
-    a.numCams = doNew ? mb->numCams : mp.numCams;
-    a.packetStride = doNew ? mb->packetStride : mp.packetStride;
+    a.numCams = doNew ? mb->numCams : pend.numCams;
+    a.packetStride = doNew ? mb->packetStride : pend.packetStride;
     if (doNew) {
-        uint32_t parts = (uint32_t)grid_for((size_t)mb->capacity, 256 * 4);
-        if (parts < 1) parts = 1;
-        a.claimBlocks = (uint32_t)mb->numBins * parts;
-        // entries per lane of the multi-camera walk by the shard's size: 4 from 32 MB of entries on, else 8
-        a.walkShort = c->numEntries * sizeof(VoxelEntry) >= ((size_t)32 << 20) ? 1u : 0u;
-        a.walkBlocks = (uint32_t)grid_for(c->numEntries, kFlattenThreads * (a.walkShort ? kEntriesPerLaneShort : kEntriesPerLane));
-        // the walk-free multi-camera frame (flatten_variant 4; not with the overflow list: holes and chains take the reference's walk)
-        a.walkIndexed = (c->flattenVariant == kWalkIndexed && !(c->fp.flags & kFlagOverflow)) ? 1u : 0u;
-        if (a.walkIndexed) a.walkBlocks = (uint32_t)grid_for(((size_t)c->ownedBuckets + 31) / 32, kFlattenThreads * kIndexWords);
-        a.partsPerBin = parts; a.numBins = (uint32_t)mb->numBins;
+        a.partsPerBin = bin_parts(mb->capacity); a.numBins = (uint32_t)mb->numBins;
+        a.claimBlocks = a.numBins * a.partsPerBin;
+        a.walkShort = multi_walk_short(c) ? 1u : 0u;
+        a.walkIndexed = multi_walk_indexed(c) ? 1u : 0u;
+        a.walkBlocks = multi_walk_blocks(c);
         a.capacity = mb->capacity; a.binStride = mb->binStride;
         a.binsNew = mb->bins + (size_t)mb->frameStride * b;
         a.binFrame = mb->perBatch ? b : -1;
@@ -409,70 +403,49 @@ static int launch_multi_pipelined(vh_context *c, const MultiBatch *mb, int b, co
     }
     a.commitBlocks = hasOld ? (uint32_t)c->commitBlocks : 0u;
     a.integrateBlocks = hasOld ? (uint32_t)c->pipeIntegrateGrid : 0u;
-    a.setNew = kPipeSetStride * setNew; a.setOld = kPipeSetStride * setOld; a.setClear = kPipeSetStride * ((setNew + 1) % 3);
-    a.hasNew = doNew; a.hasOld = hasOld;
     a.claimSpan = claim_span(c, a.claimBlocks, a.walkBlocks);
     a.claimRatio = claim_ratio(a.claimBlocks, a.claimSpan);
-    a.epochOld = mp.epochOld;
-    a.doneTag = mp.doneTag;
-    a.spinLimit = c->spinLimit ? c->spinLimit : kSpinLimitDefault;
-    a.packetsOld = mp.packetsOld;
-    DevPtrs dpNew = pipe_view(c, newParity);
-    dpNew.compactMask = maskOf[newParity];
-    const DevPtrs dpOld = pipe_view(c, oldParity);
-    a.claimOld = dpOld.claim; a.candOld = dpOld.candidates; a.compactOld = dpOld.compact; a.maskOld = maskOf[oldParity];
-    a.candCapacityOld = dpOld.candCapacity;
-    const int format = doNew ? c->packetFormat : mp.packetFormat;
+    a.epochOld = pend.epoch;
+    a.packetsOld = pend.packets;
+    r.dpNew.compactMask = maskOf[r.newParity];
+    a.claimOld = r.dpOld.claim; a.candOld = r.dpOld.candidates; a.compactOld = r.dpOld.compact; a.maskOld = maskOf[r.oldParity];
+    a.candCapacityOld = r.dpOld.candCapacity;
+    const bool sensor = (doNew ? c->packetFormat : pend.packetFormat) == VH_PACKET_U16;
     const bool serial = (c->fp.flags & kFlagOverflow) != 0u;
     // the fused generation role (vh_dist): sensor frames, no overflow list (its launches may be serialised inside), no band
-    const bool gen = job && job->blocks && doNew && format == VH_PACKET_U16 && !serial;
+    const bool gen = job && job->blocks && doNew && sensor && !serial;
     if (gen) a.gen = *job;
     const dim3 grid(a.commitBlocks + a.integrateBlocks + (gen ? a.gen.blocks : 0u) + a.claimBlocks + a.walkBlocks);
-    if (gen)
-        rc = a.walkIndexed ? launch(c, kPhaseFramePipelined, frame_multi_pipelined_kernel<true, false, true, true>, grid, dim3(256), c->fp, dpNew, a)
-                           : launch(c, kPhaseFramePipelined, frame_multi_pipelined_kernel<true, false, false, true>, grid, dim3(256), c->fp, dpNew, a);
-    else if (a.walkIndexed)         // (never with the overflow list, hence never serialised)
-        rc = format == VH_PACKET_U16 ? launch(c, kPhaseFramePipelined, frame_multi_pipelined_kernel<true, false, true>, grid, dim3(256), c->fp, dpNew, a)
-                                     : launch(c, kPhaseFramePipelined, frame_multi_pipelined_kernel<false, false, true>, grid, dim3(256), c->fp, dpNew, a);
-    else
-    rc = format == VH_PACKET_U16
-             ? (serial ? launch(c, kPhaseFramePipelined, frame_multi_pipelined_kernel<true, true>, grid, dim3(256), c->fp, dpNew, a)
-                       : launch(c, kPhaseFramePipelined, frame_multi_pipelined_kernel<true, false>, grid, dim3(256), c->fp, dpNew, a))
-             : (serial ? launch(c, kPhaseFramePipelined, frame_multi_pipelined_kernel<false, true>, grid, dim3(256), c->fp, dpNew, a)
-                       : launch(c, kPhaseFramePipelined, frame_multi_pipelined_kernel<false, false>, grid, dim3(256), c->fp, dpNew, a));
+    // run-time (sensor, serial, indexed, gen) -> the instantiation.  Only the builds named here exist: the generation role with
+    // sensor frames and without the list, the walk-free frame never with the list (hence never serialised).
+    using Yes = std::true_type;
+    using No = std::false_type;
+    auto go = [&](auto sensorC, auto serialC, auto indexedC, auto genC) {
+        return launch(c, kPhaseFramePipelined,
+                      frame_multi_pipelined_kernel<decltype(sensorC)::value, decltype(serialC)::value, decltype(indexedC)::value, decltype(genC)::value>,
+                      grid, dim3(256), c->fp, r.dpNew, a);
+    };
+    if (gen) rc = with_bool(a.walkIndexed != 0u, [&](auto i) { return go(Yes{}, No{}, i, Yes{}); });
+    else if (a.walkIndexed) rc = with_bool(sensor, [&](auto s) { return go(s, No{}, Yes{}, No{}); });
+    else rc = with_bool(sensor, [&](auto s) { return with_bool(serial, [&](auto q) { return go(s, q, No{}, No{}); }); });
     if (rc != VH_OK) return rc;
-    if (serial && doNew && hasOld) c->serialQueued = true;         // (its claim / walk workgroups wait: check_spin_timeouts)
+    pipe_launched(c, r, serial, doNew ? PendingFrame::kMulti : PendingFrame::kNone, hasOld, false, hasOld);
     if (doNew) {
-        mp.active = true;
-        mp.epochOld = c->fp.epoch;
-        mp.doneTag = (int32_t)(c->epochTotal & 0x7fffffffu) | 0x40000000;
-        mp.packetsOld = a.packetsNew;
-        mp.packetStride = mb->packetStride;
-        mp.numCams = mb->numCams;
-        mp.packetFormat = c->packetFormat;
-        c->pipeSet = setNew;
-        c->pipeParity = newParity;
-        c->dp.claim = dpNew.claim; c->dp.candidates = dpNew.candidates; c->dp.compact = dpNew.compact;
-    } else {
-        mp.active = false;
+        pend.epoch = c->fp.epoch;
+        pend.packets = a.packetsNew;
+        pend.packetStride = mb->packetStride;
+        pend.numCams = mb->numCams;
+        pend.packetFormat = c->packetFormat;
     }
-    c->occupiedCounter = kCompactCount;
-    c->compactArmed = false;
-    c->foldA = -1;
-    if (c->profiling && hasOld) c->profiledFrames += 1;
     return VH_OK;
 }
 
-// the pending multi-camera frame's deferred half in a launch of its own (flush_pending: every observer comes through it)
-static int flush_multi_pending(vh_context *c)
+// can this context run multi-camera frames over num_bins bins of `capacity` records in one launch each?  (the waiting workgroups
+// of a serialised launch: its claim slices and the tiles of the 4-entries-per-lane walk)
+static bool multi_can_pipeline(const vh_context *c, int32_t num_bins, int32_t capacity)
 {
-    if (!c->multiPend.active) return VH_OK;
-    const int rc = launch_multi_pipelined(c, nullptr, 0);
-    if (rc != VH_OK) return rc;
-    VH_HIP(hipGetLastError());
-    return VH_OK;
+    return can_pipeline(c, (uint32_t)num_bins * bin_parts(capacity) + (uint32_t)grid_for(c->numEntries, kFlattenThreads * kEntriesPerLaneShort));
 }
-
 
 // `batch` multi-camera frames applied one after the other, each as the fused pair of launches
 // (new lock epoch; {claim bins || walk}; {commit + integrate}).
@@ -480,14 +453,11 @@ static int flush_multi_pending(vh_context *c)
 // before it hands vh_apply_frames_batch_gen the jobs instead of launching the generation itself.
 static bool multi_can_fuse_generation(const vh_context *c, int32_t num_bins, int32_t capacity)
 {
-    uint32_t parts = (uint32_t)grid_for((size_t)capacity, 256 * 4);
-    if (parts < 1) parts = 1;
     // (not the walk-free launch, flatten_variant 4: it has no 17 us walk for the generating workgroups' chain to end inside, and it
     // leaves most of the chip to a generation launched beside it -- one rank, frames/s: separate launches 96.0 k, fused with 3 / 4 / 6 / 2
     // groups per workgroup 90.2 / 87.6 / 82.3 / 72.6 k, 1 group 39.7 k; profiles/r05_fused_generation_ab.txt, box 9)
-    return c->pipelineShards && c->fp.bucketSize <= kMaxPipelinedBucket && !c->viewBlocks && !(c->fp.flags & kFlagOverflow) &&
-           c->packetFormat == VH_PACKET_U16 && !(c->fp.allocBand > 0.0f) && c->flattenVariant != kWalkIndexed &&
-           serial_launch_pays(c, (uint32_t)num_bins * parts + (uint32_t)grid_for(c->numEntries, kFlattenThreads * kEntriesPerLaneShort));
+    return c->pipelineShards && multi_can_pipeline(c, num_bins, capacity) && !(c->fp.flags & kFlagOverflow) &&
+           c->packetFormat == VH_PACKET_U16 && !(c->fp.allocBand > 0.0f) && c->flattenVariant != kWalkIndexed;
 }
 
 // ... and does it pay?  A generating workgroup's chain (6 tiles, ~11 us beside a walk) has to end inside the launch: it does where the
@@ -531,13 +501,12 @@ static int vh_apply_frames_batch_gen(vh_context *c, int32_t batch, const int32_t
         packet_stride < (size_t)batch * packet_frame_stride)
         return fail(VH_ERR_INVALID_ARGUMENT, "bad stride");
     DeviceGuard guard(c->device);
-    { const int frc = flush_single_pending(c); if (frc != VH_OK) return frc; }    // (a pending multi-camera half rides along)
+    { const int frc = flush_pending(c, PendingFrame::kSingle); if (frc != VH_OK) return frc; }    // (a pending multi-camera half rides along)
     {
         const int rc = ensure_candidates(c, (size_t)num_bins * (size_t)(capacity - 1));
         if (rc != VH_OK) return rc;
     }
-    uint32_t parts = (uint32_t)grid_for((size_t)capacity, 256 * 4);
-    if (parts < 1) parts = 1;
+    const uint32_t parts = bin_parts(capacity);
     const uint32_t scanBlocks = (uint32_t)grid_for(c->numEntries, kFlattenThreads * kEntriesPerLane);
     const uint32_t commitBlocks = (uint32_t)c->commitBlocks;
     // One launch per multi-camera frame (frame_multi_pipelined_kernel, vh_shard.hip): the commit + TSDF update of frame
@@ -546,15 +515,14 @@ static int vh_apply_frames_batch_gen(vh_context *c, int32_t batch, const int32_t
     // the next batch -- B launches -- or in the flush any observer does first.
     // Same conditions as the single-camera pipeline (bucketSize <= 16, not a view table; with the overflow list the frames are
     // serialised inside the launch).
-    if (c->pipelineShards && c->fp.bucketSize <= kMaxPipelinedBucket && !c->viewBlocks &&
-        serial_launch_pays(c, (uint32_t)num_bins * parts + (uint32_t)grid_for(c->numEntries, kFlattenThreads * kEntriesPerLaneShort))) {
+    if (c->pipelineShards && multi_can_pipeline(c, num_bins, capacity)) {
         int rc = ensure_pipeline_buffers(c);
         if (rc != VH_OK) return rc;
         if ((rc = c->maskBuf2.reserve(c->numEntries, "maskBuf2")) != VH_OK) return rc;      // (first use)
-        MultiPending &mp = c->multiPend;
+        const PendingFrame &pend = c->pend;
         // a pending half of another shape (camera count, packet layout) cannot share a launch with this batch's frames
-        if (mp.active && (mp.numCams != num_cams || mp.packetStride != packet_stride || mp.packetFormat != c->packetFormat) &&
-            (rc = flush_multi_pending(c)) != VH_OK)
+        if (pend.kind == PendingFrame::kMulti && (pend.numCams != num_cams || pend.packetStride != packet_stride || pend.packetFormat != c->packetFormat) &&
+            (rc = flush_pending(c, PendingFrame::kMulti)) != VH_OK)
             return rc;
         MultiBatch mb;
         mb.bins = reinterpret_cast<const int4 *>(d_bins); mb.packets = d_packets;
@@ -566,18 +534,18 @@ static int vh_apply_frames_batch_gen(vh_context *c, int32_t batch, const int32_t
             bool doNew = true;
             // at the epoch wrap vh_reset_mutexes clears the claim words, which the pending frame still needs: it is
             // served by a launch of its own first
-            if (mp.active && c->fp.epoch >= kMaxClaimEpoch) doNew = false;
+            if (pend.kind == PendingFrame::kMulti && c->fp.epoch >= kMaxClaimEpoch) doNew = false;
             if ((rc = launch_multi_pipelined(c, doNew ? &mb : nullptr, b, doNew && jobs ? jobs + b : nullptr)) != VH_OK) return rc;
             if (doNew) {
                 if (b == 0 && c->multiFirstEvent) VH_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(c->multiFirstEvent), c->stream));
                 ++b;
             }
         }
-        if (c->pipelineShards < 2 && (rc = flush_multi_pending(c)) != VH_OK) return rc;
+        if (c->pipelineShards < 2 && (rc = flush_pending(c, PendingFrame::kMulti)) != VH_OK) return rc;
         VH_HIP(hipGetLastError());
         return VH_OK;
     }
-    { const int frc = flush_multi_pending(c); if (frc != VH_OK) return frc; }
+    { const int frc = flush_pending(c, PendingFrame::kMulti); if (frc != VH_OK) return frc; }
     for (int b = 0; b < batch; ++b) {
         int rc = vh_reset_mutexes(c);
         if (rc != VH_OK) return rc;
@@ -589,13 +557,11 @@ static int vh_apply_frames_batch_gen(vh_context *c, int32_t batch, const int32_t
                     c->fusedParity, claim_span(c, (uint32_t)num_bins * parts, scanBlocks),
                     claim_ratio((uint32_t)num_bins * parts, claim_span(c, (uint32_t)num_bins * parts, scanBlocks)), perBatch ? b : -1);
         if (rc == VH_OK)
-            rc = c->packetFormat == VH_PACKET_U16
-                     ? launch(c, kPhaseFrameCommitIntegrate, frame_multi_commit_integrate_kernel<true>,
-                              dim3(commitBlocks + (uint32_t)c->integrateGrid), dim3(256), c->fp, c->dp, num_cams,
-                              packets, packet_stride, commitBlocks, c->fusedParity)
-                     : launch(c, kPhaseFrameCommitIntegrate, frame_multi_commit_integrate_kernel<false>,
+            rc = with_bool(c->packetFormat == VH_PACKET_U16, [&](auto sensor) {
+                return launch(c, kPhaseFrameCommitIntegrate, frame_multi_commit_integrate_kernel<decltype(sensor)::value>,
                               dim3(commitBlocks + (uint32_t)c->integrateGrid), dim3(256), c->fp, c->dp, num_cams,
                               packets, packet_stride, commitBlocks, c->fusedParity);
+            });
         if (rc != VH_OK) return rc;
         c->fusedParity ^= 1;
         c->compactArmed = false;
@@ -621,9 +587,7 @@ extern "C" int vh_insert_bins(vh_context *c, const int32_t *d_bins, int32_t num_
         const int rc = ensure_candidates(c, (size_t)num_bins * (size_t)(capacity - 1));
         if (rc != VH_OK) return rc;
     }
-    int gx = grid_for((size_t)capacity, 256 * 4);
-    if (gx < 1) gx = 1;
-    int rc = launch(c, kPhaseClaim, claim_bins_kernel, dim3(gx, num_bins), dim3(256), c->fp, c->dp,
+    int rc = launch(c, kPhaseClaim, claim_bins_kernel, dim3(bin_parts(capacity), num_bins), dim3(256), c->fp, c->dp,
                     reinterpret_cast<const int4 *>(d_bins), capacity, bin_stride);
     if (rc == VH_OK) rc = launch(c, kPhaseCommit, alloc_commit_kernel, dim3(32), dim3(256), c->fp, c->dp);
     if (rc != VH_OK) return rc;
@@ -650,11 +614,10 @@ extern "C" int vh_integrate_packets(vh_context *c, int32_t num_cams, const float
                     dim3(grid_for(c->numEntries, kFlattenThreads * kEntriesPerLane)), dim3(kFlattenThreads), c->fp,
                     c->dp, (uint32_t)c->numEntries, num_cams, d_packets, stride);
     if (rc == VH_OK)
-        rc = c->packetFormat == VH_PACKET_U16
-                 ? launch(c, kPhaseIntegrate, integrate_multi_kernel<true>, dim3(c->integrateGrid), dim3(256), c->fp, c->dp,
-                          num_cams, d_packets, stride)
-                 : launch(c, kPhaseIntegrate, integrate_multi_kernel<false>, dim3(c->integrateGrid), dim3(256), c->fp,
-                          c->dp, num_cams, d_packets, stride);
+        rc = with_bool(c->packetFormat == VH_PACKET_U16, [&](auto sensor) {
+            return launch(c, kPhaseIntegrate, integrate_multi_kernel<decltype(sensor)::value>, dim3(c->integrateGrid), dim3(256), c->fp, c->dp,
+                          num_cams, d_packets, stride);
+        });
     if (rc != VH_OK) return rc;
     if (c->profiling) c->profiledFrames += 1;
     VH_HIP(hipGetLastError());

@@ -50,12 +50,44 @@ __global__ __launch_bounds__(256) void frame_scan_claim_kernel(const FrameParams
     }
 }
 
+// The words a per-frame counter set consists of: of the two-launch frame (two sets, by parity) ...
+__device__ __forceinline__ void clear_fused_set(int32_t *counters, int parity)
+{
+    counters[kScanCount + parity] = 0;
+    counters[kScanCountB + parity] = 0;
+    counters[kNewCount + parity] = 0;
+    counters[kFusedCand + parity] = 0;
+}
+// ... and of the pipelined frame (three, rotating; `set` = kPipeSetStride * index)
+__device__ __forceinline__ void clear_pipe_set(int32_t *counters, int set)
+{
+    counters[kPipeScan + set] = 0;
+    counters[kPipeScanB + set] = 0;
+    counters[kPipeNew + set] = 0;
+    counters[kPipeCand + set] = 0;
+    counters[kPipeWinners + set] = 0;
+}
+// The close of a two-launch frame's commit phase.  Only the `workers` commit workgroups that served candidates take a ticket (a
+// word that every workgroup of a large grid increments costs tens of microseconds): the last of them publishes the occupied count
+// and clears the counter set of the other parity for the next frame.  scanCountB: end B of the single-camera frame's two-ended
+// list (vh_walk.hip); the multi-camera frame has none and passes a literal 0.  (The pipelined kernels close in the same way over
+// the rotating sets, each in its own lines: DESIGN_LOG.md.)
+__device__ __forceinline__ void close_commit_fused(int32_t *counters, int workers, int parity, int scanCount, int scanCountB, int demanded)
+{
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const int ticket = atomicAdd(counters + kCommitTicket, 1);
+        if (ticket == workers - 1) {
+            counters[kCompactCount] = scanCount + scanCountB + atomicAdd(counters + kNewCount + parity, 0);
+            counters[kLastCandidates] = demanded;
+            clear_fused_set(counters, parity ^ 1);
+            counters[kCommitTicket] = 0;
+        }
+    }
+}
 // Launch 2: the first commitBlocks workgroups serve the candidates (one candidate per
 // workgroup pass: lane 0 inserts, then all 256 lanes integrate the new block and it is
 // appended to the compact list); the others stride over the entries the walk found.
-// Only the commit workgroups take a ticket (a word that every workgroup of a large grid
-// increments costs tens of microseconds): the last of them publishes the occupied count
-// and clears the counter set of the other parity for the next frame.
 // Depth: where the TSDF update reads a pixel's camera z -- DepthPlane on &verts[0].z or DepthSensor.
 template <class Depth>
 __device__ __forceinline__ void frame_commit_integrate(const FrameParams &fp, const DevPtrs &dp, const Depth &verts,
@@ -90,19 +122,7 @@ __device__ __forceinline__ void frame_commit_integrate(const FrameParams &fp, co
         if (inserted) integrate_block(fp, dp, newEntry, verts);
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        __threadfence();
-        const int ticket = atomicAdd(dp.counters + kCommitTicket, 1);
-        if (ticket == workers - 1) {
-            dp.counters[kCompactCount] = scanCount + scanCountB + atomicAdd(dp.counters + kNewCount + parity, 0);
-            dp.counters[kLastCandidates] = demanded;
-            dp.counters[kScanCount + (parity ^ 1)] = 0;
-            dp.counters[kScanCountB + (parity ^ 1)] = 0;
-            dp.counters[kNewCount + (parity ^ 1)] = 0;
-            dp.counters[kFusedCand + (parity ^ 1)] = 0;
-            dp.counters[kCommitTicket] = 0;
-        }
-    }
+    close_commit_fused(dp.counters, workers, parity, scanCount, scanCountB, demanded);
 }
 
 template <class Depth>
@@ -345,18 +365,9 @@ __device__ __forceinline__ void frame_pipelined(const FrameParams &fpNew, const 
         if (ticket == workers - 1) {
             counters[kCompactCount] = scanOld + counters[kPipeScanB + a.setOld] + atomicAdd(counters + kPipeNew + a.setOld, 0);
             counters[kLastCandidates] = demandedOld;
-            counters[kPipeScan + a.setClear] = 0;
-            counters[kPipeScanB + a.setClear] = 0;
-            counters[kPipeNew + a.setClear] = 0;
-            counters[kPipeCand + a.setClear] = 0;
-            counters[kPipeWinners + a.setClear] = 0;
-            if (!a.hasNew) {                       // flush launch: the set a new frame would have filled is unused: the next
-                counters[kPipeScan + a.setNew] = 0;    // run starts on it (the host keeps rotating), and finds it empty
-                counters[kPipeScanB + a.setNew] = 0;
-                counters[kPipeNew + a.setNew] = 0;
-                counters[kPipeCand + a.setNew] = 0;
-                counters[kPipeWinners + a.setNew] = 0;
-            }
+            clear_pipe_set(counters, a.setClear);
+            if (!a.hasNew) clear_pipe_set(counters, a.setNew);      // flush launch: the set a new frame would have filled is unused: the next
+                                                                    // run starts on it (the host keeps rotating), and finds it empty
             counters[kPipeHeapFree + a.setNew] = atomicAdd(counters + kHeapCounter, 0) + 1;   // what the next launch starts with
             counters[kCommitTicket] = 0;
             if (serial) {                          // every committer fenced before its ticket: the table is settled
@@ -367,13 +378,30 @@ __device__ __forceinline__ void frame_pipelined(const FrameParams &fpNew, const 
     }
 }
 
+// The builds of the pipelined launch (kLean).  A lean build has both frames' option flags, the walk and the claim form folded in
+// when the kernel is BUILT; the host picks it when the context's state is exactly its lean_build() (vh_api_frame.hip: lean_for).
+enum : int {
+    kLeanNone = 0,             // the generic build: flags, walk and claim form are read at run time
+    kLeanShort = 1,            // the reference's walk, 4 entries per lane (the default of a table inside the Infinity Cache)
+    kLeanShortNt = 2,          // ... with non-temporal walk loads (a table beyond it)
+    kLeanRayDda = 3,           // 1 / 2 with the ray-DDA band, VH_BAND_RAY_DDA -- builds that exist with kBand only
+    kLeanRayDdaNt = 4,
+    kLeanIndexed = 5,          // 1 / 2 with the occupancy-index walk in place of the reference's -- the walk-free frame, no band
+    kLeanIndexedNt = 6,
+    kLeanIndexedWave = 7,      // 5 / 6 with a launch tile per wave in the claim role, claim_tile_wave -- the walk-free frame of a
+    kLeanIndexedWaveNt = 8,    // large image (as a run-time switch of builds 5 / 6 it cost the 640x480 frame 8.9 -> 9.45 us)
+    kLeanBuilds = 9
+};
+struct LeanBuild { uint32_t flags; bool indexed, claimPerWave; };
+constexpr LeanBuild lean_build(int kLean)
+{
+    return {kFlagWalkShort | (kLean % 2 == 0 ? kFlagWalkNt : 0u) | (kLean == kLeanRayDda || kLean == kLeanRayDdaNt ? kFlagBandRayDda : 0u),
+            kLean >= kLeanIndexed, kLean >= kLeanIndexedWave};
+}
 // kBand: the new frame allocates a truncation band (vh_set_alloc_band > 0); false = the reference's frame, without the band code
-// kLean != 0: the option flags of both frames are known when the kernel is BUILT -- 1: only the 4-entries-per-lane walk
-// (the default of a table inside the Infinity Cache), 2: that plus non-temporal walk loads (a table beyond it) -- and the walk
-// is the reference's: everything the flags guard (overflow list, DDA band, TSDF-update variants, the other walk forms) is
+// kLean != kLeanNone: everything the flags guard (overflow list, DDA band, TSDF-update variants, the other walk forms) is
 // folded away by the compiler: 3.3 k instead of 6.8 k instructions; same box, same process: C2 18.35 -> 17.57 us, C3 69.4 ->
-// 68.4.  The host picks this build when the context's flags are exactly those.  (Folding the semantics and a bucket size of
-// 5 in as well: C2 17.2 but C3 70.2; one at a time: the semantics C2 17.9 / C3 68.4, the bucket size 17.8 / 75.2, the shard's
+// 68.4.  (Folding the semantics and a bucket size of 5 in as well: C2 17.2 but C3 70.2; one at a time: the semantics C2 17.9 / C3 68.4, the bucket size 17.8 / 75.2, the shard's
 // bucket range 17.45 / 69.0 against 17.6 / 68.5 -- not done: what the compiler makes of a smaller kernel is not monotone.
 // The same builds of the two-launch kernels: no difference (C2 16.27 + 4.45 us either way, C3 63.0 + 11.7 / 63.4 + 11.4).)
 // (Eight waves per SIMD instead of the seven the 106 SGPRs allow -- __launch_bounds__(256, 8): 78 SGPRs, 129 instead of 100 of
@@ -384,18 +412,13 @@ __global__ __launch_bounds__(256) void frame_pipelined_kernel(FrameParams fpNew,
                                                               FrameParams fpOld, const DevPtrs dpOld,
                                                               const Depth depthOld, PipeArgs a)
 {
-    if (kLean != 0) {
-        // (3 / 4: the same two with the ray-DDA band, VH_BAND_RAY_DDA -- builds that exist with kBand only)
-        // (5 / 6: the first two with the occupancy-index walk in place of the reference's -- the walk-free frame, no band)
-        // (7 / 8: 5 / 6 with a launch tile per wave in the claim role, claim_tile_wave -- the walk-free frame of a large image)
-        constexpr uint32_t flags = (kLean == 2 || kLean == 4 || kLean == 6 || kLean == 8 ? (kFlagWalkShort | kFlagWalkNt) : kFlagWalkShort) |
-                                   (kLean == 3 || kLean == 4 ? kFlagBandRayDda : 0u);
-        fpNew.flags = flags;
-        fpOld.flags = flags;
-        a.walkIndexed = kLean >= 5 ? 1u : 0u;
+    constexpr LeanBuild lean = lean_build(kLean);
+    if (kLean != kLeanNone) {
+        fpNew.flags = lean.flags;
+        fpOld.flags = lean.flags;
+        a.walkIndexed = lean.indexed ? 1u : 0u;
     }
-    a.claimPerWave = (kLean == 7 || kLean == 8) ? 1u : 0u;      // (builds of their own: carried as a run-time switch by builds 5 / 6 it
-                                                                //  cost the 640x480 walk-free frame 8.9 -> 9.45 us)
+    a.claimPerWave = lean.claimPerWave ? 1u : 0u;
     frame_pipelined<In, Depth, kBand, kSerial>(fpNew, dpNew, inNew, fpOld, dpOld, depthOld, a);
 }
 

@@ -268,19 +268,7 @@ __global__ __launch_bounds__(256) void frame_multi_commit_integrate_kernel(const
             integrate_block_multi<kSensor>(fp, dp, newEntry, newMask, numCams, packets, packetStride);
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        __threadfence();
-        const int ticket = atomicAdd(dp.counters + kCommitTicket, 1);
-        if (ticket == workers - 1) {
-            dp.counters[kCompactCount] = scanCount + atomicAdd(dp.counters + kNewCount + parity, 0);
-            dp.counters[kLastCandidates] = demanded;
-            dp.counters[kScanCount + (parity ^ 1)] = 0;
-            dp.counters[kScanCountB + (parity ^ 1)] = 0;      // (end B of the single-camera frame's list, vh_walk.hip)
-            dp.counters[kNewCount + (parity ^ 1)] = 0;
-            dp.counters[kFusedCand + (parity ^ 1)] = 0;
-            dp.counters[kCommitTicket] = 0;
-        }
-    }
+    close_commit_fused(dp.counters, workers, parity, scanCount, 0, demanded);
 }
 
 // The multi-camera frame in ONE launch (vh_apply_frames_batch with the option "pipeline_shards", on by default): the
@@ -483,18 +471,8 @@ __global__ __launch_bounds__(256) void frame_multi_pipelined_kernel(const FrameP
         if (ticket == workers - 1) {
             counters[kCompactCount] = scanOld + atomicAdd(counters + kPipeNew + a.setOld, 0);
             counters[kLastCandidates] = demandedOld;
-            counters[kPipeScan + a.setClear] = 0;
-            counters[kPipeScanB + a.setClear] = 0;
-            counters[kPipeNew + a.setClear] = 0;
-            counters[kPipeCand + a.setClear] = 0;
-            counters[kPipeWinners + a.setClear] = 0;
-            if (!a.hasNew) {
-                counters[kPipeScan + a.setNew] = 0;
-                counters[kPipeScanB + a.setNew] = 0;
-                counters[kPipeNew + a.setNew] = 0;
-                counters[kPipeCand + a.setNew] = 0;
-                counters[kPipeWinners + a.setNew] = 0;
-            }
+            clear_pipe_set(counters, a.setClear);
+            if (!a.hasNew) clear_pipe_set(counters, a.setNew);
             counters[kPipeHeapFree + a.setNew] = atomicAdd(counters + kHeapCounter, 0) + 1;
             counters[kCommitTicket] = 0;
             if (serial) {
