@@ -112,6 +112,11 @@ public:
     void deintegrateDepth(const float4x4 &oldPose, const uint16_t *d_depth, const float kInv[9]);
     /* ... and in again at the corrected pose: deintegrateDepth(oldPose) + integrate(newPose) */
     void reintegrateDepth(const float4x4 &oldPose, const float4x4 &newPose, const uint16_t *d_depth, const float kInv[9]);
+    /* One model into another (vh_merge, voxelhash.h "one model into another"): the TSDF of `src` fused into this table under
+     * the rigid row-major 4x4 srcToDst (src world metres -> this model's); mode = VH_SAMPLE_NEAREST or VH_SAMPLE_TRILINEAR; the
+     * voxel sizes may differ.  src is only read.  garbageCollect() directly afterwards frees the candidate blocks that stayed
+     * empty.  Synchronises. */
+    void merge(const SDF_Hashtable &src, const float srcToDst[16], int mode, vh_merge_stats *stats = nullptr);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

@@ -811,6 +811,63 @@ int vh_fusion_step_sdf(vh_context *ctx, struct vh_icp *icp, const uint16_t *d_de
                        struct vh_icp_system *last, int32_t *iterations);
 
 /* ------------------------------------------------------------------ */
+/* one model into another                                              */
+/* ------------------------------------------------------------------ */
+/* Merging: the TSDF held by src is fused into dst under the rigid transform src_to_dst -- submaps whose relative pose a loop
+ * closure has corrected, a second session joined to a first, a model re-anchored in another frame or re-gridded to another voxel
+ * size, a bucket-range shard pulled into one table (tests/merge_ref.py is the rule in executable form; the
+ * reference has none).  IEEE fp32, every multiply and add rounded on its own, in the order written here: the same two models
+ * and transform give the same voxel bits.
+ *   T = src_to_dst as fp32, row-major: src world metres -> dst world metres; the caller guarantees it is rigid.  Tinv = the
+ *   library's cofactor inverse of T (the routine of vh_set_pose).  vs_s, vs_d: the two voxel sizes, which may differ.  trunc,
+ *   wmax: DST's truncation and integrationWeightMax.
+ *   1. Candidates.  For every allocated entry of src with key k (chained overflow entries included) the eight corners e of the
+ *     box [8k - 0.5, 8k + 8] per axis in src voxel units -- a low corner is (float)(8k) - 0.5f, a high one (float)(8k + 8) -- are
+ *     transformed: x = e * vs_s, q_r = ((T[r][0] * x + T[r][1] * y) + T[r][2] * z) + T[r][3], u_r = q_r / vs_d.  Per axis lo / hi
+ *     = the minimum / maximum over the corners, gmin = (int)ceilf(lo), gmax = (int)ceilf(hi) - 1; the entry's candidates are all
+ *     block keys gmin >> 3 .. gmax >> 3 per axis.  A block with any u failing |u| < 2^30 (NaN included) is skipped
+ *     (skipped_blocks) and contributes nothing.  The box holds every point whose trilinear cell or nearest voxel lies in block
+ *     k, so the candidates are a superset of the dst blocks that can receive a sample (up to rounding at the rim, where this
+ *     rule is the rule): with T = I and equal voxel sizes the candidate of k is k (and, for voxel sizes that are not powers of
+ *     two, now and then k + 1, which stays empty); under a rotation about 3.3 x the source's blocks, a third to a half of
+ *     which stay empty.
+ *   2. Allocation.  The candidate keys are inserted into dst through the claim + commit path of vh_insert_bins, one lock epoch
+ *     (vh_reset_mutexes) per round, until no candidate is missing or a round allocates nothing (buckets full, heap empty);
+ *     with the overflow list, too.  Which slot and heap block a key gets is free, as for frames.  dst may be a shard: keys of
+ *     other bucket ranges are not its business and are not counted as unplaced.  The call holds at most 2^24 candidate records
+ *     (duplicates counted; 256 MiB of scratch, allocated by the first call into a context and kept): more is refused with
+ *     VH_ERR_OUT_OF_MEMORY before dst changes.
+ *   3. Update, over the distinct candidate blocks present in dst, each once.  For dst voxel g: p_a = (float)g_a * vs_d,
+ *     q = Tinv . p (rows summed as above), (s, w) = the `mode` sample of SRC at q by the rule of vh_sample_sdf ("the model as a
+ *     distance field" above: u = q / vs_s, domain, validity, nearest or trilinear sdf and weight; blocks of another shard are
+ *     absent; view tables and the overflow list as there).  No sample (s is NaN) or !(w > 0): the voxel is untouched.
+ *     Otherwise s = s >= 0 ? fminf(trunc, s) : fmaxf(-trunc, s) and, with the stored voxel {os, ow}:
+ *       !(ow > 0): the voxel becomes {s, fminf(wmax, w)} -- a voxel that holds nothing contributes nothing, so a nearest-voxel
+ *         identity merge into an empty model is an exact copy;
+ *       otherwise sdf = ((os * ow) + (s * w)) / (ow + w), weight = fminf(wmax, ow + w).
+ *   4. Afterwards dst's compact list and vh_counters.occupied are the blocks the update ran over, so vh_garbage_collect(dst, ..)
+ *     directly after the call frees the candidate blocks that stayed empty (the pairing to use).  allocated_total and
+ *     heap_exhausted move as the commit path moves them; the epoch advances by `rounds`; dst's pose is unchanged; src is only
+ *     read.  A src without candidates (empty, or wholly outside the domain): VH_OK, nothing changes.
+ * Ordering: a pending pipelined frame of either context is launched first; the call orders itself behind src's stream with an
+ * event (recorded there, awaited on dst's stream), its kernels run on dst's stream, and it synchronises dst's stream (round
+ * counters, stats).  In vh_kernel_times the key generation and the bin claim count as alloc_claim_ms, the commit and the
+ * missing-key count as alloc_commit_ms, the list as flatten_ms, the update as integrate_ms.
+ * VH_ERR_INVALID_ARGUMENT, and nothing is changed or launched: a NULL context or matrix; src == dst; contexts on different
+ * devices; dst holding an imported view; an unknown mode; an entry of T or of its inverse that is not finite. */
+typedef struct vh_merge_stats {
+    uint32_t source_blocks;   /* allocated entries of src that were walked */
+    uint32_t skipped_blocks;  /* of those, outside the domain: they contribute nothing */
+    uint64_t candidates;      /* candidate records generated, duplicates counted */
+    uint32_t allocated;       /* blocks this call allocated in dst */
+    uint32_t blocks;          /* distinct blocks of dst that received the update (= occupied afterwards) */
+    uint64_t unplaced;        /* candidate records (duplicates counted) whose key is not in dst after the last round */
+    uint32_t rounds;          /* lock epochs the allocation used */
+} vh_merge_stats;
+int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst[16], int32_t mode /* VH_SAMPLE_NEAREST | VH_SAMPLE_TRILINEAR */,
+             vh_merge_stats *stats /* host, may be NULL */);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to

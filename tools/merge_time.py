@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Time of vh_merge after a workload's pose loop: the model is merged into an EMPTY twin (same parameters) under a fixed
+oblique transform, trilinear, once per cycle into a fresh twin.  Reported separately, from the per-dispatch HIP events of
+vh_set_profiling on the twin (medians and minima over the cycles of one process):
+
+  update launch        integrate_ms: merge_update_kernel alone
+  allocation rounds    alloc_claim_ms + alloc_commit_ms: the two key-generation passes, then per round the bin claim, the commit and
+                       the missing-key count
+  list                 flatten_ms: the compact list through the mark bits
+  whole call           HIP events around vh_merge on the twin's stream (the call synchronises: host time between launches included)
+
+and, alternating with the merges in the same process, the yardstick of the update launch: vh_sample_sdf (trilinear, with
+weight) on the source over as many points as the update samples -- the positions of the voxels of the blocks it ran over.
+
+  python tools/merge_time.py [--workload C2] [--frames N] [--cycles K]
+"""
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def oblique():
+    a = np.array((0.3, 1.0, -0.45))
+    a = a / np.linalg.norm(a)
+    t = math.radians(27.0)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + math.sin(t) * K + (1 - math.cos(t)) * (K @ K)
+    T[:3, 3] = (0.113, -0.071, 0.057)
+    return T.astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="C2")
+    ap.add_argument("--frames", type=int, default=0, help="poses fused before the measurement (0: the workload's)")
+    ap.add_argument("--cycles", type=int, default=7)
+    a = ap.parse_args()
+    import torch
+
+    import voxelhashing_demo_amd as V
+    from bench import WORKLOADS
+    from voxelhashing_demo_amd import synth
+    if not torch.cuda.is_available():
+        raise SystemExit("merge_time.py needs a GPU: there is nothing to time without one")
+    wl = WORKLOADS[a.workload]
+    Wd, Ht = wl["width"], wl["height"]
+    n = a.frames or wl["frames"]
+    poses = synth.camera_loop(wl.get("loop", wl["frames"]))[:n]
+    prims = synth.room_primitives()
+    kw = dict(numBuckets=wl["buckets"], numVoxelBlocks=wl["blocks"], voxelSize=wl["voxel"])
+    src = V.SDFHashtable(V.default_params(**kw), Wd, Ht, V.SEM_PINHOLE)
+    kinv = np.linalg.inv(synth.K_matrix(Wd, Ht).astype(np.float64)).astype(np.float32)
+    for p in poses:
+        z = synth.render_room_verts(p, Wd, Ht, prims, device="cuda")[..., 2]
+        src.integrate_depth(p, torch.round(z * 5000.0).clamp(0, 65535).to(torch.int32).to(torch.uint16).contiguous(), kinv)
+    src.synchronize()
+    T = oblique()
+    print(f"{a.workload}: {n} poses, {len(src.allocated())} source blocks, {Wd}x{Ht}, voxel {wl['voxel']}")
+
+    rows, stats, points = [], None, None
+    for cycle in range(a.cycles + 1):                        # (cycle 0 warms up: scratch allocation, code load)
+        dst = V.SDFHashtable(V.default_params(**kw), Wd, Ht, V.SEM_PINHOLE)
+        dst.set_profiling(True)
+        dst.synchronize()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record()
+        stats = dst.merge(src, T, V.SAMPLE_TRILINEAR)
+        e[1].record()
+        kt = dst.kernel_times()
+        if points is None:                                   # the update's sample positions, once
+            keys = torch.from_numpy(np.ascontiguousarray(dst.compact()["pos"]).astype(np.int64)).cuda()
+            i = torch.arange(512, device="cuda")
+            local = torch.stack([i & 7, (i >> 3) & 7, i >> 6], 1)
+            g = (keys[:, None, :] * 8 + local[None, :, :]).reshape(-1, 3).to(torch.float32) * wl["voxel"]
+            Tinv = torch.from_numpy(np.linalg.inv(T.astype(np.float64)).astype(np.float32)).cuda()
+            points = (g @ Tinv[:3, :3].T + Tinv[:3, 3]).contiguous()
+            sdf = torch.empty(len(points), dtype=torch.float32, device="cuda")
+            wgt = torch.empty(len(points), dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+        e[2].record()
+        src.sample_sdf_into(points, sdf, wgt)
+        e[3].record()
+        torch.cuda.synchronize()
+        if cycle:
+            rows.append((1e3 * kt["integrate_ms"], 1e3 * (kt["alloc_claim_ms"] + kt["alloc_commit_ms"]), 1e3 * kt["flatten_ms"],
+                         1e3 * e[0].elapsed_time(e[1]), 1e3 * e[2].elapsed_time(e[3])))
+        dst.close()
+    r = np.array(rows)
+    print(f"  vh_merge_stats: {stats}")
+    print(f"  update over {stats['blocks']} blocks = {len(points)} samples; {int(torch.isfinite(sdf).sum())} of the yardstick's points have a sample")
+    for name, col in (("update launch", 0), ("allocation rounds", 1), ("list", 2), ("whole call", 3), ("vh_sample_sdf (yardstick)", 4)):
+        print(f"  {name:28s} median {np.median(r[:, col]):9.1f} us  min {r[:, col].min():9.1f} us  over {len(r)} cycles")
+    print(f"  ratio of medians (update / yardstick): {np.median(r[:, 0]) / np.median(r[:, 4]):.3f}")
+
+
+if __name__ == "__main__":
+    main()

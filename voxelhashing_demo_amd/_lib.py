@@ -78,6 +78,15 @@ class IcpSystem(C.Structure):
     _fields_ = [("JTJ", C.c_double * 36), ("JTr", C.c_double * 6), ("error", C.c_double), ("count", C.c_uint32)]
 
 
+class MergeStats(C.Structure):
+    """vh_merge_stats."""
+    _fields_ = [("source_blocks", C.c_uint32), ("skipped_blocks", C.c_uint32), ("candidates", C.c_uint64),
+                ("allocated", C.c_uint32), ("blocks", C.c_uint32), ("unplaced", C.c_uint64), ("rounds", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class PtrContainer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "d_heap", "d_hashTable", "d_compactifiedHashTable", "d_hashTableBucketMutex", "d_SDFBlocks",
@@ -148,6 +157,7 @@ SIGNATURES = {
     "vh_deintegrate": (C.c_int, [_vp, _fp, _vp]),
     "vh_deintegrate_depth": (C.c_int, [_vp, _fp, _vp, _fp]),
     "vh_reintegrate_depth": (C.c_int, [_vp, _fp, _fp, _vp, _fp]),
+    "vh_merge": (C.c_int, [_vp, _vp, _fp, _i32, C.POINTER(MergeStats)]),
     "vh_sdf_build_system": (C.c_int, [_vp, _vp, _vp, _fp, _f, C.POINTER(IcpSystem)]),
     "vh_sdf_residuals": (C.c_int, [_vp, _vp, _vp, _fp, _f, _vp, _vp, _vp, C.POINTER(IcpSystem)]),
     "vh_sdf_align": (C.c_int, [_vp, _vp, _vp, _f, C.c_int32, C.POINTER(C.c_double), C.POINTER(IcpSystem), C.POINTER(C.c_int32)]),

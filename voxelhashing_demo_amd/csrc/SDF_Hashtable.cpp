@@ -198,6 +198,11 @@ void SDF_Hashtable::reintegrateDepth(const float4x4 &oldPose, const float4x4 &ne
     check(vh_reintegrate_depth(ctx_, oldPose.entries, newPose.entries, d_depth, kInv), "reintegrateDepth");
 }
 
+void SDF_Hashtable::merge(const SDF_Hashtable &src, const float srcToDst[16], int mode, vh_merge_stats *stats)
+{
+    check(vh_merge(ctx_, src.ctx_, srcToDst, mode, stats), "merge");      // (src is only read)
+}
+
 uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
 {
     std::vector<float> pos, nrm;

@@ -145,6 +145,17 @@ struct DevBuf {
     size_t size() const { return n; }
 };
 
+// vh_merge (vh_api_merge.hip): scratch of the first call a context receives as dst, kept; a context that never merges has none
+struct MergeScratch {
+    DevBuf<int4> bin;                      // the candidate records as one key bin: {count, 0, 0, 0}, then {x, y, z, rank}
+    DevBuf<unsigned long long> words;      // MergeWord[]: the counts of the call
+    hipEvent_t ordered = nullptr;          // recorded on src's stream, awaited on dst's
+    MergeScratch() = default;
+    MergeScratch(const MergeScratch &) = delete;
+    MergeScratch &operator=(const MergeScratch &) = delete;
+    ~MergeScratch() { if (ordered) (void)hipEventDestroy(ordered); }
+};
+
 struct vh_context {
     HashTableParams params;
     FrameParams fp;
@@ -226,6 +237,7 @@ struct vh_context {
     // vh_extract_mesh_indexed: scratch of its first call, kept
     DevBuf<uint32_t> meshWords;            // per listed block 512 words {vertex prefix << 7 | edge mask}, then the per-block vertex counts, then listPos[ptr >> 9]
     DevBuf<unsigned long long> meshVertexTotals;   // the vertex scan's tile totals, then {listed blocks, vertices, triangles}
+    MergeScratch merge;                    // vh_merge into this context: scratch of its first call, kept
 };
 
 struct DeviceGuard {
@@ -575,6 +587,7 @@ static int ensure_candidates(vh_context *c, size_t need)
 #include "vh_api_sample.hip"
 #include "vh_api_rays.hip"
 #include "vh_api_deintegrate.hip"
+#include "vh_api_merge.hip"
 #include "vh_api_dropin.hip"
 #include "vh_api_icp.hip"
 #include "vh_api_track.hip"

@@ -27,6 +27,9 @@
 //                      (no counterpart in the reference)
 //   vh_track.hip       point-to-SDF camera tracking: the ICP's round with the trilinear sample of the model as residual and
 //                      its gradient as normal (no counterpart in the reference)
+//   vh_merge.hip       one model fused into another under a rigid transform: candidate keys from the source's blocks through the
+//                      bin insertion path, then the TSDF update's launch shape with the distance-field sample as the measurement
+//                      (no counterpart in the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -52,3 +55,4 @@
 #include "vh_sample.hip"
 #include "vh_rays.hip"
 #include "vh_track.hip"
+#include "vh_merge.hip"

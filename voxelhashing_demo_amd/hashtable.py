@@ -198,6 +198,19 @@ class SDFHashtable:
         L.check(self._lib.vh_reintegrate_depth(self._h, po, pn, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float))),
                 "vh_reintegrate_depth")
 
+    # ---- one model into another ----
+    def merge(self, src, src_to_dst, mode: int = L.SAMPLE_TRILINEAR) -> dict:
+        """vh_merge: the model of `src` (another SDFHashtable on this device) fused into this one under the rigid 4x4
+        src_to_dst (src world metres -> this model's).  Voxel sizes may differ.  Synchronises this context's stream; src is only
+        read.  Returns vh_merge_stats as a dict; garbage_collect() directly afterwards frees the candidate blocks that stayed
+        empty."""
+        if not isinstance(src, SDFHashtable):
+            raise TypeError("merge: src must be an SDFHashtable")
+        _, pp = _pose16(src_to_dst)
+        st = L.MergeStats()
+        L.check(self._lib.vh_merge(self._h, src._h, pp, int(mode), C.byref(st)), "vh_merge")
+        return st.as_dict()
+
     def integrate_batch(self, poses, verts_list, normals_list=None):
         """len(poses) frames in len(poses) + 1 launches (pipelined frames, flushed at the end); equals
         integrate() frame by frame."""
