@@ -117,6 +117,15 @@ public:
      * voxel sizes may differ.  src is only read.  garbageCollect() directly afterwards frees the candidate blocks that stayed
      * empty.  Synchronises. */
     void merge(const SDF_Hashtable &src, const float srcToDst[16], int mode, vh_merge_stats *stats = nullptr);
+    /* The model in colour (vh_integrate_depth_color / vh_integrate_color, voxelhash.h "the model in colour"): d_rgba = W*H words
+     * r | g << 8 | b << 16 registered to the depth image, averaged into the voxels within `band` metres of the surface with a
+     * window of weightMax samples (1..255; 0 only sweeps the colour of voxels that hold nothing).  withDepth: the depth frame is
+     * fused first (one RGB-D frame in one call).  Asynchronous. */
+    void integrateColor(const float4x4 &pose, const uint16_t *d_depth, const float kInv[9], const uint32_t *d_rgba, float band,
+                        int weightMax = 255, bool withDepth = false);
+    /* ... and read back at world points through host buffers (vh_sample_color_host): points = 3 floats per point; rgba = one
+     * word per point, r | g << 8 | b << 16 | 0xFF << 24, or 0 where there is no colour.  Synchronises. */
+    void sampleColor(const std::vector<float> &points, int mode, std::vector<uint32_t> &rgba);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

@@ -868,6 +868,78 @@ int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst[16], int32
              vh_merge_stats *stats /* host, may be NULL */);
 
 /* ------------------------------------------------------------------ */
+/* the model in colour                                                 */
+/* ------------------------------------------------------------------ */
+/* The registered colour image of an RGB-D frame fused into the voxels near the surface, and read back at points, at mesh
+ * vertices or per pixel of a raycast (tests/color_ref.py is the rule in executable form; the reference has
+ * none).  Voxel stays {sdf, weight}: colour lives in a second volume of one uint32 per voxel, numVoxelBlocks * 512 words, the
+ * voxel at volume index ptr + i having its word at ptr + i.  IEEE fp32, every operation rounded on its own, in the order
+ * written here: the same model and images give the same words.
+ *   Word: r | g << 8 | b << 16 | w << 24, w = the colour sample count, 1..255.  The word 0 means "no colour".
+ *   The volume is allocated, zeroed, by the first colour-fusing call into a context and kept: half the bytes of the SDF volume.
+ *   A failed allocation returns VH_ERR_OUT_OF_MEMORY and nothing changes.  A context that never fuses colour allocates nothing
+ *   and behaves exactly as before.
+ * FUSING.  d_rgba is W*H pixels registered to the depth image, one little-endian word per pixel: byte 0 red, byte 1 green,
+ * byte 2 blue, byte 3 ignored.
+ *   Block set: every allocated entry of this table (or shard) that passes blockInFrustum for `pose` -- the compact set of
+ *     vh_set_pose(pose) + vh_flatten, as for vh_deintegrate, chained overflow entries included.  No block is allocated or freed.
+ *   Per voxel of a listed block, with the stored voxel {os, ow} and its colour word c:
+ *     1. !(ow > 0): the word becomes 0 and nothing else happens to this voxel -- a voxel that holds nothing has no colour,
+ *        which also sweeps out the colour a de-integration orphaned.
+ *     2. The camera point by the context's semantics, project, the image bounds test, the depth read, depth <= 0 rejects:
+ *        all exactly as in vh_integrate's update.  s = depth - cz; no truncation is involved.
+ *     3. !(fabsf(s) <= band) rejects: colour belongs to the surface (the reference's default truncation of 1 m would paint
+ *        a metre of free space).
+ *     4. A rejected voxel is untouched.
+ *     5. weight_max == 0: no sample is added; the call is the sweep of step 1 only.
+ *     6. Otherwise, with (R, G, B) the pixel at (sx, sy) and w = c >> 24, per channel
+ *          f = ((float)old * (float)w + (float)in) / (float)(w + 1),  new = (uint32_t)(f + 0.5f), truncating.
+ *     7. w' = min(w + 1, weight_max): at the cap the average keeps moving, with window weight_max.
+ *   vh_integrate_color reads the uint16 sensor image with vh_integrate_depth's arithmetic, vh_integrate_color_map the .z of a
+ *   float4 vertex map.  vh_integrate_depth_color is exactly vh_integrate_depth followed by vh_integrate_color.
+ *   Afterwards the context's pose is `pose`, the compact list and vh_counters.occupied are the flatten's; the lock epoch, the
+ *   heap, the hash table and the SDF volume are unchanged.  A pending pipelined frame is launched first.  The calls only
+ *   enqueue: they read nothing back and do not synchronise.  In vh_kernel_times the launch counts as integrate_ms, its flatten
+ *   as flatten_ms.  Both semantics; with or without the overflow list; on shards every shard is called with the same arguments
+ *   and colours its own blocks.
+ *   VH_ERR_INVALID_ARGUMENT, with nothing changed: a NULL argument; band not finite or <= 0; weight_max outside 0..255; a
+ *   context that holds an imported view.
+ * KEEPING IT CONSISTENT.  vh_delete_blocks and vh_garbage_collect zero the colour words of the blocks they free (blocks are
+ * handed out zeroed).  vh_load_snapshot clears the colour volume: ptrs are re-dealt and snapshots do not carry colour (the
+ * file format is unchanged).  vh_deintegrate*, vh_merge, view records and the text dump neither carry nor remove colour; the
+ * pairing after a de-integration is vh_integrate_color(old_pose, ..., weight_max = 0), which sweeps the emptied voxels.
+ * vh_has_color: 0 or 1.  vh_clear_color zeroes the volume if there is one (enqueues only).  vh_download_color synchronises;
+ * VH_ERR_INVALID_ARGUMENT when there is no volume or the range is beyond it.
+ * READING.  Output word: r | g << 8 | b << 16 | 0xFF << 24; 0 = no colour (real black is 0xFF000000).  The domain,
+ * u = p / voxelSize, which voxel or cell, and voxel validity are those of vh_sample_sdf ("the model as a distance field").
+ *   VH_SAMPLE_NEAREST: the nearest voxel's colour, if that voxel is valid and its word has w > 0.
+ *   VH_SAMPLE_TRILINEAR: a sample iff the sdf rule has one (eight valid corners) and all eight words have w > 0; per channel
+ *     the lerp nest of vh_sample_sdf's sdf on the eight (float) channel values, out = (uint32_t)(f + 0.5f).
+ *   No volume yet (or a context that holds an imported view, whose records carry no colour): every output is 0, VH_OK.
+ *   vh_sample_color_map: points in the camera frame; a point with .z == 0 has no colour, otherwise
+ *     q_r = ((T[r][0] * x + T[r][1] * y) + T[r][2] * z) + T[r][3] (vh_sdf_align's formula) and the rule above at q.
+ *   vh_raycast_color is exactly vh_raycast_maps followed by vh_sample_color_map over its vertex map.
+ *   The device calls only enqueue, behind every queued frame; they allocate nothing and change nothing; on shards the blocks
+ *   of other shards are absent.  Argument checks are vh_sample_sdf's (plus a NULL pose); vh_sample_color_host takes host
+ *   buffers and synchronises, as vh_sample_sdf_host. */
+int vh_integrate_color(vh_context *ctx, const float pose[16], const uint16_t *d_depth, const float k_inv[9],
+                       const uint32_t *d_rgba, float band, int32_t weight_max);
+int vh_integrate_color_map(vh_context *ctx, const float pose[16], const vh_float4 *d_verts, const uint32_t *d_rgba,
+                           float band, int32_t weight_max);
+int vh_integrate_depth_color(vh_context *ctx, const float pose[16], const uint16_t *d_depth, const float k_inv[9],
+                             const uint32_t *d_rgba, float band, int32_t weight_max);
+int vh_has_color(vh_context *ctx);
+int vh_clear_color(vh_context *ctx);
+int vh_download_color(vh_context *ctx, size_t first_voxel, uint32_t *host_dst, size_t count);   /* synchronises */
+int vh_sample_color(vh_context *ctx, int32_t mode, uint64_t n, const float *d_points /* n*3, world metres */,
+                    uint32_t *d_rgba_out /* n words */);
+int vh_sample_color_host(vh_context *ctx, int32_t mode, uint64_t n, const float *h_points, uint32_t *h_rgba_out);
+int vh_sample_color_map(vh_context *ctx, int32_t mode, const float pose[16], uint64_t n,
+                        const vh_float4 *d_points /* camera frame */, uint32_t *d_rgba_out);
+int vh_raycast_color(vh_context *ctx, const float pose[16], float t_min, float t_max, float *d_depth_out,
+                     vh_float4 *d_vertices_out, vh_float4 *d_normals_out, int32_t mode, uint32_t *d_rgba_out);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to
@@ -877,7 +949,8 @@ int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst[16], int32
 int vh_dump_sdf_text(vh_context *ctx, const char *path);
 /* Binary snapshot of the model (hash table, heap, counters, the 4 KiB block of every
  * allocated entry) and its restore into a context created with the same configuration;
- * fusing can continue after vh_load_snapshot as if never interrupted.  Both synchronise. */
+ * fusing can continue after vh_load_snapshot as if never interrupted.  Both synchronise.
+ * Snapshots do not carry colour: vh_load_snapshot clears the colour volume ("the model in colour"). */
 int vh_save_snapshot(vh_context *ctx, const char *path);
 int vh_load_snapshot(vh_context *ctx, const char *path);
 

@@ -203,6 +203,20 @@ void SDF_Hashtable::merge(const SDF_Hashtable &src, const float srcToDst[16], in
     check(vh_merge(ctx_, src.ctx_, srcToDst, mode, stats), "merge");      // (src is only read)
 }
 
+void SDF_Hashtable::integrateColor(const float4x4 &pose, const uint16_t *d_depth, const float kInv[9], const uint32_t *d_rgba, float band,
+                                   int weightMax, bool withDepth)
+{
+    check(withDepth ? vh_integrate_depth_color(ctx_, pose.entries, d_depth, kInv, d_rgba, band, weightMax)
+                    : vh_integrate_color(ctx_, pose.entries, d_depth, kInv, d_rgba, band, weightMax), "integrateColor");
+}
+
+void SDF_Hashtable::sampleColor(const std::vector<float> &points, int mode, std::vector<uint32_t> &rgba)
+{
+    const uint64_t n = points.size() / 3;
+    rgba.assign((size_t)n, 0u);
+    check(vh_sample_color_host(ctx_, mode, n, points.data(), rgba.data()), "sampleColor");
+}
+
 uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
 {
     std::vector<float> pos, nrm;

@@ -238,6 +238,7 @@ struct vh_context {
     DevBuf<uint32_t> meshWords;            // per listed block 512 words {vertex prefix << 7 | edge mask}, then the per-block vertex counts, then listPos[ptr >> 9]
     DevBuf<unsigned long long> meshVertexTotals;   // the vertex scan's tile totals, then {listed blocks, vertices, triangles}
     MergeScratch merge;                    // vh_merge into this context: scratch of its first call, kept
+    DevBuf<uint32_t> color;                // the colour volume (vh_api_color.hip): one word per voxel, of the first colour-fusing call, kept
 };
 
 struct DeviceGuard {
@@ -366,6 +367,8 @@ static int flush_pending(vh_context *c, PendingFrame::Kind kind);      // ... if
 struct MultiBatch;
 static int launch_multi_pipelined(vh_context *c, const MultiBatch *mb, int b, const GenJob *job = nullptr);      // vh_api_shard.hip
 static int settle(vh_context *c);              // ... and folds a two-ended compact list into the dense one (observers)
+static int release_color(vh_context *c);       // vh_api_color.hip: the colour words of the blocks a deletion freed, if there is a colour volume
+static hipError_t reset_color(vh_context *c);  // ... and the whole volume back to "no colour"
 
 static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_context **out)
 {
@@ -588,6 +591,7 @@ static int ensure_candidates(vh_context *c, size_t need)
 #include "vh_api_rays.hip"
 #include "vh_api_deintegrate.hip"
 #include "vh_api_merge.hip"
+#include "vh_api_color.hip"
 #include "vh_api_dropin.hip"
 #include "vh_api_icp.hip"
 #include "vh_api_track.hip"

@@ -14,6 +14,8 @@ static int sweep_and_release(vh_context *c)
         rc = launch(c, kPhaseGc, gc_sweep_kernel, dim3(256), dim3(256), c->fp, c->dp);
     }
     if (rc != VH_OK) return rc;
+    rc = release_color(c);                           // (reads the freed list the release consumes)
+    if (rc != VH_OK) return rc;
     rc = launch(c, kPhaseGc, gc_release_kernel, dim3(1024), dim3(256), c->dp);
     if (rc != VH_OK) return rc;
     rc = launch(c, kPhaseGc, gc_finish_kernel, dim3(1), dim3(1), c->dp, c->occupiedCounter);
@@ -360,6 +362,7 @@ extern "C" int vh_load_snapshot(vh_context *c, const char *path)
     DeviceGuard guard(c->device);
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }
     hipError_t e = reset_model(c);
+    if (e == hipSuccess) e = reset_color(c);         // ptrs are re-dealt and the file carries no colour
     const size_t words = ((size_t)c->ownedBuckets + 31) / 32;
     std::vector<uint32_t> bits(words, 0u), macro(kMacroBits / 32, 0u);
     std::vector<Voxel> block(kBlockVoxels);

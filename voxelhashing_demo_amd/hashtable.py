@@ -211,6 +211,99 @@ class SDFHashtable:
         L.check(self._lib.vh_merge(self._h, src._h, pp, int(mode), C.byref(st)), "vh_merge")
         return st.as_dict()
 
+    # ---- the model in colour ----
+    def _check_rgba(self, rgba, what):
+        if not isinstance(rgba, int):
+            if rgba.element_size() != 4 or rgba.is_floating_point():
+                raise ValueError(f"{what}: the colour image must hold one 32-bit word per pixel (r | g << 8 | b << 16)")
+            if rgba.numel() != self.width * self.height:
+                raise ValueError(f"{what}: the colour image must hold height * width pixels")
+            if not rgba.is_cuda:
+                raise ValueError(f"{what}: the colour image must be a CUDA tensor")
+
+    def integrate_color(self, pose, depth_u16, k_inv, rgba, band: float, weight_max: int = 255):
+        """Asynchronous: the colour image `rgba` [H, W] (one word per pixel, registered to the uint16 depth image) averaged
+        into the voxels within `band` metres of the surface, over the blocks `pose` sees.  weight_max: 1..255, the window of
+        the running average; 0 only sweeps the colour of voxels that hold nothing (the pairing after a de-integration).
+        The first call allocates the colour volume."""
+        _, pp = _pose16(pose)
+        self._check_depth_u16(depth_u16, "integrate_color")
+        self._check_rgba(rgba, "integrate_color")
+        k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        L.check(self._lib.vh_integrate_color(self._h, pp, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                             _dev_ptr(rgba), float(band), int(weight_max)), "vh_integrate_color")
+
+    def integrate_color_map(self, pose, verts, rgba, band: float, weight_max: int = 255):
+        """The same with the depth taken from the .z of a float4 vertex map [H, W, 4]."""
+        _, pp = _pose16(pose)
+        self._check_verts(verts, "integrate_color_map")
+        self._check_rgba(rgba, "integrate_color_map")
+        L.check(self._lib.vh_integrate_color_map(self._h, pp, _dev_ptr(verts), _dev_ptr(rgba), float(band), int(weight_max)),
+                "vh_integrate_color_map")
+
+    def integrate_depth_color(self, pose, depth_u16, k_inv, rgba, band: float, weight_max: int = 255):
+        """One RGB-D frame: integrate_depth followed by integrate_color."""
+        _, pp = _pose16(pose)
+        self._check_depth_u16(depth_u16, "integrate_depth_color")
+        self._check_rgba(rgba, "integrate_depth_color")
+        k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        L.check(self._lib.vh_integrate_depth_color(self._h, pp, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   _dev_ptr(rgba), float(band), int(weight_max)), "vh_integrate_depth_color")
+
+    def has_color(self) -> bool:
+        return bool(self._lib.vh_has_color(self._h))
+
+    def clear_color(self):
+        L.check(self._lib.vh_clear_color(self._h), "vh_clear_color")
+
+    def color_volume(self) -> np.ndarray:
+        """The colour words of the whole volume (uint32, r | g << 8 | b << 16 | count << 24; 0 = no colour), indexed like
+        sdf_blocks().  Raises when the context has no colour volume."""
+        out = np.empty(self.params.numVoxelBlocks * 512, np.uint32)
+        L.check(self._lib.vh_download_color(self._h, 0, out.ctypes.data_as(C.c_void_p), out.size), "vh_download_color")
+        return out
+
+    def block_colors(self, ptr: int) -> np.ndarray:
+        """The 512 colour words of the block at voxel index `ptr` (an entry's ptr)."""
+        out = np.empty(512, np.uint32)
+        L.check(self._lib.vh_download_color(self._h, int(ptr), out.ctypes.data_as(C.c_void_p), out.size), "vh_download_color")
+        return out
+
+    def sample_color_into(self, points, rgba, mode: int = L.SAMPLE_TRILINEAR, n: int = None):
+        """vh_sample_color into a caller-owned device buffer: points [n, 3] float32 (world metres), rgba [n] 32-bit words
+        (r | g << 8 | b << 16 | 0xFF << 24; 0 = no colour).  Asynchronous on the context's stream."""
+        n = int(points.shape[0]) if n is None else int(n)
+        L.check(self._lib.vh_sample_color(self._h, int(mode), n, _dev_ptr(points), _dev_ptr(rgba)), "vh_sample_color")
+        return rgba
+
+    def sample_color(self, points, mode: int = L.SAMPLE_TRILINEAR):
+        """The colour at world points [n, 3] (float32 CUDA tensor) as a uint32 CUDA tensor [n]."""
+        import torch
+        rgba = torch.empty((int(points.shape[0]),), dtype=torch.uint32, device=points.device)
+        return self.sample_color_into(points, rgba, mode)
+
+    def sample_color_map_into(self, pose, points4, rgba, mode: int = L.SAMPLE_TRILINEAR, n: int = None):
+        """vh_sample_color_map: camera-frame float4 points [n, 4] (a vertex map; .z == 0: no point) moved by `pose`."""
+        _, pp = _pose16(pose)
+        n = int(points4.numel() // 4) if n is None else int(n)
+        L.check(self._lib.vh_sample_color_map(self._h, int(mode), pp, n, _dev_ptr(points4), _dev_ptr(rgba)),
+                "vh_sample_color_map")
+        return rgba
+
+    def render_color(self, pose, t_min: float = 0.1, t_max: float = 5.0, mode: int = L.SAMPLE_TRILINEAR):
+        """The model seen from `pose` in colour (vh_raycast_color): (depth [H, W], vertices [H, W, 4], normals [H, W, 4],
+        rgba [H, W] uint32) as CUDA tensors; a pixel without a hit or without colour is 0."""
+        import torch
+        _, pp = _pose16(pose)
+        with torch.cuda.device(self.device_index()):
+            depth = torch.empty((self.height, self.width), dtype=torch.float32, device="cuda")
+            verts = torch.empty((self.height, self.width, 4), dtype=torch.float32, device="cuda")
+            nrm = torch.empty((self.height, self.width, 4), dtype=torch.float32, device="cuda")
+            rgba = torch.empty((self.height, self.width), dtype=torch.uint32, device="cuda")
+        L.check(self._lib.vh_raycast_color(self._h, pp, t_min, t_max, _dev_ptr(depth), _dev_ptr(verts), _dev_ptr(nrm), int(mode),
+                                           _dev_ptr(rgba)), "vh_raycast_color")
+        return depth, verts, nrm, rgba
+
     def integrate_batch(self, poses, verts_list, normals_list=None):
         """len(poses) frames in len(poses) + 1 launches (pipelined frames, flushed at the end); equals
         integrate() frame by frame."""
@@ -330,10 +423,12 @@ class SDFHashtable:
         """(vertices, triangles) of the indexed mesh inside `region`, None = the whole model."""
         return self.extract_mesh_indexed_into(0, 0, None, None, None, region)
 
-    def extract_mesh_indexed(self, region=None, normals: bool = False):
+    def extract_mesh_indexed(self, region=None, normals: bool = False, colors: bool = False):
         """The mesh of extract_mesh() in indexed form, made on the GPU: (vertices [V, 3] float32, faces [T, 3] int32) and
         per-vertex normals [V, 3] with normals=True.  One vertex per cell edge with a sign change (never merged by position);
-        vertices[faces] has the bits of extract_mesh(), triangle for triangle."""
+        vertices[faces] has the bits of extract_mesh(), triangle for triangle.  colors=True appends the per-vertex colour
+        words [V] uint32 (r | g << 8 | b << 16 | 0xFF << 24; 0 = no colour; mesh_io.save_ply takes them as they are): the
+        trilinear colour sample at the vertex where it has one, else the nearest voxel's."""
         import torch
         nv, nt = self.mesh_counts(region)
         if nv > 2**31 - 1:
@@ -346,8 +441,12 @@ class SDFHashtable:
             got = self.extract_mesh_indexed_into(nv, nt, pos, idx, nrm, region)
             if got != (nv, nt):
                 raise L.VoxelHashError(f"the model changed between the count ({nv}, {nt}) and the extraction {got}")
-        out = (pos.cpu().numpy(), idx.cpu().numpy())
-        return out + (nrm.cpu().numpy(),) if normals else out
+        out = (pos.cpu().numpy(), idx.cpu().numpy()) + ((nrm.cpu().numpy(),) if normals else ())
+        if colors:
+            tri = self.sample_color(pos, L.SAMPLE_TRILINEAR).cpu().numpy()
+            near = self.sample_color(pos, L.SAMPLE_NEAREST).cpu().numpy()
+            out += (np.where(tri != 0, tri, near),)
+        return out
 
     # ---- the model as a distance field ----
     def sample_sdf_into(self, points, sdf, weight=None, gradient=None, mode: int = L.SAMPLE_TRILINEAR, n: int = None):
