@@ -126,6 +126,16 @@ public:
     /* ... and read back at world points through host buffers (vh_sample_color_host): points = 3 floats per point; rgba = one
      * word per point, r | g << 8 | b << 16 | 0xFF << 24, or 0 where there is no colour.  Synchronises. */
     void sampleColor(const std::vector<float> &points, int mode, std::vector<uint32_t> &rgba);
+    /* Colour through merging, de-integration and saved models (voxelhash.h, the section of that name): merge() with src's colour
+     * carried along in the same launch (vh_merge_color; weightMax 1..255), an RGB-D frame taken back out
+     * (vh_deintegrate_depth_color) or moved to its corrected pose (vh_reintegrate_depth_color), and the colour words as a file
+     * beside a snapshot (vh_save_color / vh_load_color; load after the snapshot). */
+    void mergeColor(const SDF_Hashtable &src, const float srcToDst[16], int mode, int weightMax = 255, vh_merge_stats *stats = nullptr);
+    void deintegrateDepthColor(const float4x4 &oldPose, const uint16_t *d_depth, const float kInv[9], const uint32_t *d_rgba, float band);
+    void reintegrateDepthColor(const float4x4 &oldPose, const float4x4 &newPose, const uint16_t *d_depth, const float kInv[9],
+                               const uint32_t *d_rgba, float band, int weightMax = 255);
+    void saveColor(const char *path);
+    void loadColor(const char *path);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

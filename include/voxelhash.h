@@ -906,8 +906,11 @@ int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst[16], int32
  *   context that holds an imported view.
  * KEEPING IT CONSISTENT.  vh_delete_blocks and vh_garbage_collect zero the colour words of the blocks they free (blocks are
  * handed out zeroed).  vh_load_snapshot clears the colour volume: ptrs are re-dealt and snapshots do not carry colour (the
- * file format is unchanged).  vh_deintegrate*, vh_merge, view records and the text dump neither carry nor remove colour; the
- * pairing after a de-integration is vh_integrate_color(old_pose, ..., weight_max = 0), which sweeps the emptied voxels.
+ * file format is unchanged); vh_save_color / vh_load_color keep the words in a file beside the snapshot.  vh_deintegrate*,
+ * vh_merge, view records and the text dump neither carry nor remove colour; the pairing after a plain de-integration is
+ * vh_integrate_color(old_pose, ..., weight_max = 0), which sweeps the emptied voxels.  The calls that do carry colour through
+ * those steps are vh_merge_color, vh_deintegrate_color / vh_deintegrate_depth_color / vh_reintegrate_depth_color and
+ * vh_save_color / vh_load_color: "colour through merging, de-integration and saved models" below.
  * vh_has_color: 0 or 1.  vh_clear_color zeroes the volume if there is one (enqueues only).  vh_download_color synchronises;
  * VH_ERR_INVALID_ARGUMENT when there is no volume or the range is beyond it.
  * READING.  Output word: r | g << 8 | b << 16 | 0xFF << 24; 0 = no colour (real black is 0xFF000000).  The domain,
@@ -940,6 +943,64 @@ int vh_raycast_color(vh_context *ctx, const float pose[16], float t_min, float t
                      vh_float4 *d_vertices_out, vh_float4 *d_normals_out, int32_t mode, uint32_t *d_rgba_out);
 
 /* ------------------------------------------------------------------ */
+/* colour through merging, de-integration and saved models             */
+/* ------------------------------------------------------------------ */
+/* The calls above composed with colour (tests/merge_color_ref.py is the rule in executable form).  Every call
+ * above keeps its behaviour.  IEEE fp32, every operation rounded on its own, in the order written; words as in "the model in
+ * colour".
+ * MERGING.  vh_merge_color is vh_merge -- its candidates, allocation, ordering, stats, refusals and what it leaves afterwards,
+ * and for every dst voxel its TSDF update with the same bits -- with a colour step in the same update launch, at the same point
+ * u = (Tinv . g * vs_d) / vs_s, through the source blocks the TSDF sample resolved (the table is not walked a second time).
+ *   Colour sample of src, (rgb_s, w_s):
+ *     VH_SAMPLE_NEAREST: the nearest voxel's word, if its count w_s = word >> 24 is > 0.
+ *     VH_SAMPLE_TRILINEAR: a sample iff all eight corner words have a count > 0 (the corners are valid: the TSDF sample
+ *       exists); per channel vh_sample_color's lerp nest and (uint32_t)(f + 0.5f); w_s = the minimum of the eight counts.
+ *   Colour step, only where the TSDF step happened (the sample is not NaN and w > 0) and a colour sample exists.  With dst's
+ *   word c and w_d = c >> 24:
+ *     w_d == 0: the word becomes rgb_s | min(w_s, weight_max) << 24;
+ *     otherwise per channel f = ((float)old * (float)w_d + (float)in * (float)w_s) / (float)(w_d + w_s),
+ *       new = (uint32_t)(f + 0.5f), and the count becomes min(w_d + w_s, weight_max).
+ *   So a nearest-voxel identity merge into an empty model with weight_max = 255 copies every colour word of a valid voxel
+ *   exactly, as it copies the TSDF.
+ *   A src without a colour volume, or a view table as src: the call is exactly vh_merge and allocates nothing in dst.  A src
+ *   with a volume and a dst without: dst's is allocated and zeroed before anything else changes (VH_ERR_OUT_OF_MEMORY, nothing
+ *   changed, when that fails).  src's two volumes are only read.  Refusals: vh_merge's, and weight_max outside 1..255.
+ * TAKING A FRAME'S COLOUR BACK OUT.  vh_deintegrate_color is one launch in vh_integrate_color's shape behind the step-level
+ * flatten for `pose`: block set and steps 1 to 4 of FUSING exactly (the !(ow > 0) sweep included).  For a voxel that passes,
+ * with w = c >> 24:
+ *     w == 0: untouched.  w == 1: the word becomes 0.
+ *     otherwise per channel f = ((float)old * (float)w - (float)in) / (float)(w - 1), f = fminf(fmaxf(f, 0.0f), 255.0f),
+ *       new = (uint32_t)(f + 0.5f); the count becomes w - 1.
+ *   Exactness is as for the TSDF: the inverse holds only below the colour cap (a word at weight_max has forgotten how many
+ *   samples it averaged) and only up to byte rounding.  Removing the frame that was added last brings each channel back to
+ *   within 1 of its value before that frame: the add rounds by at most 0.5, and the inverse scales that by w / (w - 1) <= 2
+ *   before it rounds to the nearest byte.  Removing an older frame, or several, lets these errors add up.
+ *   vh_deintegrate_depth_color is exactly vh_deintegrate_color(pose, ..) -- first, because it reads the TSDF weights and the
+ *   band as the frame left them -- then vh_deintegrate_depth(pose, ..), then vh_integrate_color(pose, .., weight_max = 0), the
+ *   sweep of what emptied.  vh_reintegrate_depth_color is exactly vh_deintegrate_depth_color(old_pose, ..) followed by
+ *   vh_integrate_depth_color(new_pose, .., weight_max).
+ *   Enqueue only; shards, both semantics, the overflow list and vh_kernel_times as for vh_integrate_color.
+ *   VH_ERR_INVALID_ARGUMENT, with nothing changed: a NULL argument; band not finite or <= 0; (vh_reintegrate_depth_color)
+ *   weight_max outside 0..255; a context that holds an imported view; a context without a colour volume (nothing to remove).
+ * SAVED MODELS.  vh_save_color writes the colour words to a file of its own: a header (magic, numEntries, numVoxelBlocks, the
+ * allocated count), then per allocated entry in table order its pos[3] and its 512 words.  Written to path + ".partial" and
+ * renamed, as the snapshot is; a context without a volume: VH_ERR_INVALID_ARGUMENT.  vh_load_color validates everything on
+ * the host before a device byte changes -- the header against the context, the file size, and the file's sequence of pos
+ * against the context's currently allocated entries in table order -- and a mismatch leaves the model and its colour
+ * untouched.  Then it allocates the volume if needed, clears it, and writes each record at the entry's current ptr.  The
+ * pairing is vh_save_snapshot + vh_save_color, and vh_load_snapshot followed by vh_load_color.  Both calls synchronise. */
+int vh_merge_color(vh_context *dst, vh_context *src, const float src_to_dst[16], int32_t mode, int32_t weight_max /* 1..255 */,
+                   vh_merge_stats *stats /* host, may be NULL */);
+int vh_deintegrate_color(vh_context *ctx, const float pose[16], const uint16_t *d_depth, const float k_inv[9],
+                         const uint32_t *d_rgba, float band);
+int vh_deintegrate_depth_color(vh_context *ctx, const float pose[16], const uint16_t *d_depth, const float k_inv[9],
+                               const uint32_t *d_rgba, float band);
+int vh_reintegrate_depth_color(vh_context *ctx, const float old_pose[16], const float new_pose[16], const uint16_t *d_depth,
+                               const float k_inv[9], const uint32_t *d_rgba, float band, int32_t weight_max);
+int vh_save_color(vh_context *ctx, const char *path);
+int vh_load_color(vh_context *ctx, const char *path);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to
@@ -950,7 +1011,8 @@ int vh_dump_sdf_text(vh_context *ctx, const char *path);
 /* Binary snapshot of the model (hash table, heap, counters, the 4 KiB block of every
  * allocated entry) and its restore into a context created with the same configuration;
  * fusing can continue after vh_load_snapshot as if never interrupted.  Both synchronise.
- * Snapshots do not carry colour: vh_load_snapshot clears the colour volume ("the model in colour"). */
+ * Snapshots do not carry colour: vh_load_snapshot clears the colour volume ("the model in colour").  A coloured model is
+ * saved as the pair vh_save_snapshot + vh_save_color and resumed with vh_load_snapshot followed by vh_load_color. */
 int vh_save_snapshot(vh_context *ctx, const char *path);
 int vh_load_snapshot(vh_context *ctx, const char *path);
 

@@ -6,6 +6,9 @@ process, the two alternating cycle by cycle.
                   vh_set_profiling), against integrate_ms of the step-level TSDF update of the same frame over the same compact
                   list: vh_set_pose + vh_flatten + vh_integrate_depth_map (integrate_kernel alone).  The colour launch moves at
                   most 8 KiB per block (4 KiB TSDF in, 2 KiB colour in, at most 2 KiB out), the update 8 KiB.
+  removal launch  integrate_ms of vh_deintegrate_color (color_deintegrate_kernel alone) directly behind the colour launch, with
+                  the same image and over the same list: the sample just added is taken out again, so the model the cycles
+                  see stays the same.  It reads the uint16 sensor image where the colour launch reads the vertex map.
   colour sampler  vh_sample_color against vh_sample_sdf (sdf only), both trilinear, over the same points -- the voxel positions
                   of the visible blocks, each moved into its cell -- between HIP events on the context's stream.
 
@@ -82,6 +85,8 @@ def main():
         t.kernel_times()                                      # (reset)
         t.integrate_color_map(pose, verts, rgba, band)
         colour = t.kernel_times()
+        t.deintegrate_color(pose, d16, kinv, rgba, band)
+        removal = t.kernel_times()
         t.set_pose(pose)
         t.flatten(sync=False)
         t.integrate_depth_map(verts)
@@ -96,14 +101,15 @@ def main():
         torch.cuda.synchronize()
         if cycle >= a.warmup:
             rows.append((1e3 * colour["integrate_ms"], 1e3 * update["integrate_ms"], 1e3 * colour["flatten_ms"],
-                         1e3 * e[0].elapsed_time(e[1]), 1e3 * e[2].elapsed_time(e[3])))
+                         1e3 * e[0].elapsed_time(e[1]), 1e3 * e[2].elapsed_time(e[3]), 1e3 * removal["integrate_ms"]))
     r = np.array(rows)
     coloured = int((torch.from_numpy(t.color_volume().view(np.int32)) != 0).sum())
     print(f"  {coloured} coloured voxels; {int((col != 0).sum())} of the points have a colour, {int(torch.isfinite(sdf).sum())} an sdf")
-    for name, c in (("colour launch", 0), ("update launch (yardstick)", 1), ("flatten of the colour call", 2),
+    for name, c in (("colour launch", 0), ("removal launch", 5), ("update launch (yardstick)", 1), ("flatten of the colour call", 2),
                     ("vh_sample_color", 3), ("vh_sample_sdf (yardstick)", 4)):
         print(f"  {name:30s} median {np.median(r[:, c]):9.1f} us  min {r[:, c].min():9.1f} us  over {len(r)} cycles")
     print(f"  ratio of medians (colour launch / update launch): {np.median(r[:, 0]) / np.median(r[:, 1]):.3f}")
+    print(f"  ratio of medians (removal launch / colour launch): {np.median(r[:, 5]) / np.median(r[:, 0]):.3f}")
     print(f"  ratio of medians (vh_sample_color / vh_sample_sdf): {np.median(r[:, 3]) / np.median(r[:, 4]):.3f}")
 
 

@@ -12,7 +12,13 @@ vh_set_profiling on the twin (medians and minima over the cycles of one process)
 and, alternating with the merges in the same process, the yardstick of the update launch: vh_sample_sdf (trilinear, with
 weight) on the source over as many points as the update samples -- the positions of the voxels of the blocks it ran over.
 
-  python tools/merge_time.py [--workload C2] [--frames N] [--cycles K]
+With --color the source is fused with a synthetic colour image per frame (band: three voxels) and three launches alternate in
+the one process, each cycle into fresh empty twins: the update launch of vh_merge_color (merge_color_update_kernel), the update
+launch of vh_merge (merge_update_kernel, unchanged), and vh_sample_color (trilinear) on the source over the same 512 x blocks
+points -- the second walk of the hash table that carrying colour in the same launch avoids.  Reported: medians and minima, the
+ratio of the fused launch to vh_merge's, and to the sum of the two separate passes.
+
+  python tools/merge_time.py [--workload C2] [--frames N] [--cycles K] [--color]
 """
 import argparse
 import math
@@ -35,11 +41,62 @@ def oblique():
     return T.astype(np.float32)
 
 
+def update_points(dst, T, voxel):
+    """The update's sample positions in src's frame: the voxels of the blocks dst's compact list holds, through Tinv."""
+    import torch
+    keys = torch.from_numpy(np.ascontiguousarray(dst.compact()["pos"]).astype(np.int64)).cuda()
+    i = torch.arange(512, device="cuda")
+    local = torch.stack([i & 7, (i >> 3) & 7, i >> 6], 1)
+    g = (keys[:, None, :] * 8 + local[None, :, :]).reshape(-1, 3).to(torch.float32) * voxel
+    Tinv = torch.from_numpy(np.linalg.inv(T.astype(np.float64)).astype(np.float32)).cuda()
+    return (g @ Tinv[:3, :3].T + Tinv[:3, 3]).contiguous()
+
+
+def color_cycles(a, wl, kw, src, T):
+    import torch
+
+    import voxelhashing_demo_amd as V
+    Wd, Ht = wl["width"], wl["height"]
+    rows, stats, points, col = [], None, None, None
+    for cycle in range(a.cycles + 1):                        # (cycle 0 warms up: scratch and volume allocation, code load)
+        times = []
+        for colors in (True, False):
+            dst = V.SDFHashtable(V.default_params(**kw), Wd, Ht, V.SEM_PINHOLE)
+            dst.set_profiling(True)
+            dst.synchronize()
+            stats = dst.merge(src, T, V.SAMPLE_TRILINEAR, colors=colors)
+            times.append(1e3 * dst.kernel_times()["integrate_ms"])
+            if points is None:
+                points = update_points(dst, T, wl["voxel"])
+                col = torch.empty(len(points), dtype=torch.int32, device="cuda")
+                torch.cuda.synchronize()
+            if colors:
+                coloured = int(np.count_nonzero(dst.color_volume()))
+            dst.close()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        e[0].record()
+        src.sample_color_into(points, col)
+        e[1].record()
+        torch.cuda.synchronize()
+        if cycle:
+            rows.append((times[0], times[1], 1e3 * e[0].elapsed_time(e[1])))
+    r = np.array(rows)
+    print(f"  vh_merge_stats: {stats}")
+    print(f"  update over {stats['blocks']} blocks = {len(points)} samples; {coloured} voxels of the twin received colour, "
+          f"{int((col != 0).sum())} of the sampler's points have one")
+    for name, c in (("vh_merge_color update launch", 0), ("vh_merge update launch", 1), ("vh_sample_color (second walk)", 2)):
+        print(f"  {name:32s} median {np.median(r[:, c]):9.1f} us  min {r[:, c].min():9.1f} us  over {len(r)} cycles")
+    m = np.median(r, axis=0)
+    print(f"  ratio of medians (fused / vh_merge's update): {m[0] / m[1]:.3f}")
+    print(f"  ratio of medians (fused / (vh_merge's update + vh_sample_color)): {m[0] / (m[1] + m[2]):.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="C2")
     ap.add_argument("--frames", type=int, default=0, help="poses fused before the measurement (0: the workload's)")
     ap.add_argument("--cycles", type=int, default=7)
+    ap.add_argument("--color", action="store_true", help="time vh_merge_color's update launch against vh_merge's and vh_sample_color")
     a = ap.parse_args()
     import torch
 
@@ -56,12 +113,20 @@ def main():
     kw = dict(numBuckets=wl["buckets"], numVoxelBlocks=wl["blocks"], voxelSize=wl["voxel"])
     src = V.SDFHashtable(V.default_params(**kw), Wd, Ht, V.SEM_PINHOLE)
     kinv = np.linalg.inv(synth.K_matrix(Wd, Ht).astype(np.float64)).astype(np.float32)
+    gen = torch.Generator(device="cuda").manual_seed(1)
     for p in poses:
         z = synth.render_room_verts(p, Wd, Ht, prims, device="cuda")[..., 2]
-        src.integrate_depth(p, torch.round(z * 5000.0).clamp(0, 65535).to(torch.int32).to(torch.uint16).contiguous(), kinv)
+        d16 = torch.round(z * 5000.0).clamp(0, 65535).to(torch.int32).to(torch.uint16).contiguous()
+        if a.color:
+            rgba = torch.randint(0, 1 << 24, (Ht, Wd), dtype=torch.int32, device="cuda", generator=gen)
+            src.integrate_depth_color(p, d16, kinv, rgba, 3.0 * wl["voxel"])
+        else:
+            src.integrate_depth(p, d16, kinv)
     src.synchronize()
     T = oblique()
     print(f"{a.workload}: {n} poses, {len(src.allocated())} source blocks, {Wd}x{Ht}, voxel {wl['voxel']}")
+    if a.color:
+        return color_cycles(a, wl, kw, src, T)
 
     rows, stats, points = [], None, None
     for cycle in range(a.cycles + 1):                        # (cycle 0 warms up: scratch allocation, code load)

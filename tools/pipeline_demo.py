@@ -4,8 +4,11 @@ through the C-ABI: uint16 depth -> vertex/normal maps (preProcess) -> pose from 
 against a raycast of the model (CameraTracking::Align; bypassed in the reference, Application.cpp:75)
 -> TSDF integration (SDF_Hashtable::integrate) -> periodic garbage collection.  Prints the time per
 stage and the drift against the true trajectory; --mesh writes the fused model as a triangle mesh at the end
-(welded by position on the host), --mesh-indexed the indexed mesh the GPU makes (one vertex per cell edge).
-tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply]"""
+(welded by position on the host), --mesh-indexed the indexed mesh the GPU makes (one vertex per cell edge).  --color fuses a
+synthetic colour image with every frame (vh_integrate_color_map, a band of three voxels); --snapshot writes the model at the end
+(vh_save_snapshot) and, where the model is coloured, its colour words beside it as <path>.color (vh_save_color): the pair
+load_snapshot + load_color resumes from.
+tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--snapshot out.vhsnap]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -22,6 +25,13 @@ if "--mesh-indexed" in argv:
 if "--mesh" in argv:
     MESH = argv[argv.index("--mesh") + 1]
     del argv[argv.index("--mesh"):argv.index("--mesh") + 2]
+COLOR = "--color" in argv
+if COLOR:
+    argv.remove("--color")
+SNAPSHOT = None
+if "--snapshot" in argv:
+    SNAPSHOT = argv[argv.index("--snapshot") + 1]
+    del argv[argv.index("--snapshot"):argv.index("--snapshot") + 2]
 N = int(argv[0]) if argv else 60
 gt = synth.camera_loop(500)[200:200 + N]
 prims = synth.room_primitives()
@@ -38,6 +48,12 @@ verts, normals = torch.empty((H, W, 4), device="cuda"), torch.empty((H, W, 4), d
 tp, tn = torch.empty_like(verts), torch.empty_like(verts)
 ray = torch.empty((H, W), device="cuda")
 stage = dict(preprocess=0.0, raycast_target=0.0, align=0.0, integrate=0.0, collect=0.0)
+if COLOR:
+    stage["color"] = 0.0
+    BAND = 3.0 * table.params.voxelSize
+    paint = torch.Generator(device="cuda").manual_seed(1)
+    rgba = [torch.randint(0, 1 << 24, (H, W), dtype=torch.int32, device="cuda", generator=paint) for _ in range(N)]
+    torch.cuda.synchronize()
 
 
 def timed(name, fn):
@@ -62,6 +78,8 @@ with torch.cuda.stream(stream):
             timed("align", lambda: delta.__setitem__(0, trk.Align(verts, tp, tn)))
             pose = pose @ delta[0].astype(np.float64)
         timed("integrate", lambda: table.integrate(pose.astype(np.float32), verts))
+        if COLOR:
+            timed("color", lambda: table.integrate_color_map(pose.astype(np.float32), verts, rgba[k], BAND))
         if k % 20 == 19:
             timed("collect", lambda: table.garbage_collect(0.5))
         errs.append(float(np.abs(pose[:3, 3] - np.asarray(gt[k], np.float64).reshape(4, 4)[:3, 3]).max()))
@@ -88,3 +106,9 @@ if MESH_INDEXED:
         dt = time.perf_counter() - t0
     mesh_io.save_ply(MESH_INDEXED, mv, mf, mn)
     print(f"mesh indexed: triangles={len(mf)} vertices={len(mv)} ({1e3 * dt:.1f} ms with download) -> {MESH_INDEXED}")
+if SNAPSHOT:
+    table.save_snapshot(SNAPSHOT)
+    print(f"snapshot -> {SNAPSHOT}")
+    if table.has_color():
+        table.save_color(SNAPSHOT + ".color")
+        print(f"colour words -> {SNAPSHOT}.color (load_snapshot, then load_color)")

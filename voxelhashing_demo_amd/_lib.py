@@ -168,6 +168,12 @@ SIGNATURES = {
     "vh_sample_color_host": (C.c_int, [_vp, _i32, C.c_uint64, _fp, C.POINTER(_u32)]),
     "vh_sample_color_map": (C.c_int, [_vp, _i32, _fp, C.c_uint64, _vp, _vp]),
     "vh_raycast_color": (C.c_int, [_vp, _fp, _f, _f, _vp, _vp, _vp, _i32, _vp]),
+    "vh_merge_color": (C.c_int, [_vp, _vp, _fp, _i32, _i32, C.POINTER(MergeStats)]),
+    "vh_deintegrate_color": (C.c_int, [_vp, _fp, _vp, _fp, _vp, _f]),
+    "vh_deintegrate_depth_color": (C.c_int, [_vp, _fp, _vp, _fp, _vp, _f]),
+    "vh_reintegrate_depth_color": (C.c_int, [_vp, _fp, _fp, _vp, _fp, _vp, _f, _i32]),
+    "vh_save_color": (C.c_int, [_vp, C.c_char_p]),
+    "vh_load_color": (C.c_int, [_vp, C.c_char_p]),
     "vh_sdf_build_system": (C.c_int, [_vp, _vp, _vp, _fp, _f, C.POINTER(IcpSystem)]),
     "vh_sdf_residuals": (C.c_int, [_vp, _vp, _vp, _fp, _f, _vp, _vp, _vp, C.POINTER(IcpSystem)]),
     "vh_sdf_align": (C.c_int, [_vp, _vp, _vp, _f, C.c_int32, C.POINTER(C.c_double), C.POINTER(IcpSystem), C.POINTER(C.c_int32)]),

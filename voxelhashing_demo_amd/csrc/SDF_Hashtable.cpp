@@ -217,6 +217,28 @@ void SDF_Hashtable::sampleColor(const std::vector<float> &points, int mode, std:
     check(vh_sample_color_host(ctx_, mode, n, points.data(), rgba.data()), "sampleColor");
 }
 
+void SDF_Hashtable::mergeColor(const SDF_Hashtable &src, const float srcToDst[16], int mode, int weightMax, vh_merge_stats *stats)
+{
+    check(vh_merge_color(ctx_, src.ctx_, srcToDst, mode, weightMax, stats), "mergeColor");      // (src is only read)
+}
+
+void SDF_Hashtable::deintegrateDepthColor(const float4x4 &oldPose, const uint16_t *d_depth, const float kInv[9], const uint32_t *d_rgba,
+                                          float band)
+{
+    check(vh_deintegrate_depth_color(ctx_, oldPose.entries, d_depth, kInv, d_rgba, band), "deintegrateDepthColor");
+}
+
+void SDF_Hashtable::reintegrateDepthColor(const float4x4 &oldPose, const float4x4 &newPose, const uint16_t *d_depth, const float kInv[9],
+                                          const uint32_t *d_rgba, float band, int weightMax)
+{
+    check(vh_reintegrate_depth_color(ctx_, oldPose.entries, newPose.entries, d_depth, kInv, d_rgba, band, weightMax),
+          "reintegrateDepthColor");
+}
+
+void SDF_Hashtable::saveColor(const char *path) { check(vh_save_color(ctx_, path), "saveColor"); }
+
+void SDF_Hashtable::loadColor(const char *path) { check(vh_load_color(ctx_, path), "loadColor"); }
+
 uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
 {
     std::vector<float> pos, nrm;

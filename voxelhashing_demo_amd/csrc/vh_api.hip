@@ -367,6 +367,7 @@ static int flush_pending(vh_context *c, PendingFrame::Kind kind);      // ... if
 struct MultiBatch;
 static int launch_multi_pipelined(vh_context *c, const MultiBatch *mb, int b, const GenJob *job = nullptr);      // vh_api_shard.hip
 static int settle(vh_context *c);              // ... and folds a two-ended compact list into the dense one (observers)
+static int ensure_color(vh_context *c);        // vh_api_color.hip: the colour volume, allocated and zeroed if the context has none (all or nothing)
 static int release_color(vh_context *c);       // vh_api_color.hip: the colour words of the blocks a deletion freed, if there is a colour volume
 static hipError_t reset_color(vh_context *c);  // ... and the whole volume back to "no colour"
 

@@ -1,7 +1,7 @@
-// vh_api_color.hip -- C-ABI, the model in colour: vh_integrate_color*, vh_sample_color*, vh_raycast_color, the colour volume's
-// housekeeping (kernels: vh_color.hip).  Included by vh_api.hip (same translation unit: shares fail(), VH_HIP, DeviceGuard,
+// vh_api_color.hip -- C-ABI, the model in colour: vh_integrate_color*, vh_deintegrate_color and its compositions,
+// vh_sample_color*, vh_raycast_color, vh_save_color / vh_load_color, the colour volume's housekeeping (kernels: vh_color.hip).  Included by vh_api.hip (same translation unit: shares fail(), VH_HIP, DeviceGuard,
 // launch(), flush_pending(), vh_set_pose(), vh_flatten(), vh_raycast_maps()).
-// The device calls only enqueue: no read-back, no synchronisation.  The one allocation is the colour volume itself, made and
+// The device calls only enqueue: no read-back, no synchronisation (the two file calls are host code and synchronise).  The one allocation is the colour volume itself, made and
 // zeroed by the first colour-fusing call into a context and kept.
 
 static size_t color_words(const vh_context *c) { return (size_t)c->params.numVoxelBlocks * kBlockVoxels; }
@@ -87,6 +87,170 @@ extern "C" int vh_integrate_depth_color(vh_context *c, const float pose[16], con
     { DeviceGuard guard(c->device); if ((rc = ensure_color(c)) != VH_OK) return rc; }
     rc = vh_integrate_depth(c, pose, d_depth, k_inv);
     return rc != VH_OK ? rc : vh_integrate_color(c, pose, d_depth, k_inv, d_rgba, band, weight_max);
+}
+
+// ---------------------------------------------------------------------------
+// taking a frame's colour back out
+// ---------------------------------------------------------------------------
+// integrate_color_impl's shape with the removal kernel; a context without a volume has nothing to remove
+static int check_color_removal(const vh_context *c, float band, int32_t weight_max)
+{
+    const int rc = check_color_frame(c, band, weight_max);
+    if (rc != VH_OK) return rc;
+    if (!c->color) return fail(VH_ERR_INVALID_ARGUMENT, "the context has no colour volume: there is no colour to take out");
+    return VH_OK;
+}
+
+extern "C" int vh_deintegrate_color(vh_context *c, const float pose[16], const uint16_t *d_depth, const float k_inv[9],
+                                    const uint32_t *d_rgba, float band)
+{
+    VH_TRACE("vh_deintegrate_color");
+    if (!c || !pose || !d_depth || !k_inv || !d_rgba) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_color_removal(c, band, 0);
+    if (rc != VH_OK) return rc;
+    DeviceGuard guard(c->device);
+    rc = flush_pending(c);                           // the frames queued so far are part of the model
+    if (rc == VH_OK) rc = vh_set_pose(c, pose);
+    if (rc == VH_OK) rc = vh_flatten(c, nullptr);    // (no occupied_out: the count stays on the device)
+    if (rc != VH_OK) return rc;
+    rc = launch(c, kPhaseIntegrate, color_deintegrate_kernel<DepthSensor>, dim3((unsigned)c->integrateGrid), dim3(256), c->fp, c->dp,
+                DepthSensor{d_depth, k_inv[6], k_inv[7], k_inv[8], 5000.0f}, c->color.get(), d_rgba, band);
+    if (rc != VH_OK) return rc;
+    VH_HIP(hipGetLastError());
+    return VH_OK;
+}
+
+// Compositions: every refusal of a later part is met before the first part runs.  Colour goes first -- it reads the TSDF
+// weights and the band as the frame left them -- and the sweep of what the TSDF removal emptied goes last.
+extern "C" int vh_deintegrate_depth_color(vh_context *c, const float pose[16], const uint16_t *d_depth, const float k_inv[9],
+                                          const uint32_t *d_rgba, float band)
+{
+    VH_TRACE("vh_deintegrate_depth_color");
+    if (!c || !pose || !d_depth || !k_inv || !d_rgba) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_color_removal(c, band, 0);
+    if (rc != VH_OK) return rc;
+    rc = vh_deintegrate_color(c, pose, d_depth, k_inv, d_rgba, band);
+    if (rc == VH_OK) rc = vh_deintegrate_depth(c, pose, d_depth, k_inv);
+    return rc != VH_OK ? rc : vh_integrate_color(c, pose, d_depth, k_inv, d_rgba, band, 0);
+}
+
+extern "C" int vh_reintegrate_depth_color(vh_context *c, const float old_pose[16], const float new_pose[16], const uint16_t *d_depth,
+                                          const float k_inv[9], const uint32_t *d_rgba, float band, int32_t weight_max)
+{
+    VH_TRACE("vh_reintegrate_depth_color");
+    if (!c || !old_pose || !new_pose || !d_depth || !k_inv || !d_rgba) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_color_removal(c, band, weight_max);
+    if (rc != VH_OK) return rc;
+    rc = vh_deintegrate_depth_color(c, old_pose, d_depth, k_inv, d_rgba, band);
+    return rc != VH_OK ? rc : vh_integrate_depth_color(c, new_pose, d_depth, k_inv, d_rgba, band, weight_max);
+}
+
+// ---------------------------------------------------------------------------
+// colour beside a snapshot
+// ---------------------------------------------------------------------------
+// A file of its own: header, then {pos[3], 512 words} per allocated entry in table order.  The snapshot format stays as it is;
+// the pairing is vh_load_snapshot (which clears the volume) followed by vh_load_color.
+struct ColorFileHeader {
+    char magic[8];                 // "VHCOLR01"
+    uint64_t numEntries, numAllocated;
+    uint32_t numVoxelBlocks, reserved;
+};
+struct ColorFileRecord {
+    int32_t pos[3];
+    uint32_t words[kBlockVoxels];
+};
+
+extern "C" int vh_save_color(vh_context *c, const char *path)
+{
+    if (!c || !path) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
+    if (c->viewBlocks) return fail(VH_ERR_INVALID_ARGUMENT, "a view table owns no blocks");
+    if (!c->color) return fail(VH_ERR_INVALID_ARGUMENT, "the context has no colour volume");
+    std::vector<VoxelEntry> table(c->numEntries);
+    int rc = vh_download(c, VH_BUF_HASH_TABLE, table.data(), table.size() * sizeof(VoxelEntry));     // (synchronises)
+    if (rc != VH_OK) return rc;
+    ColorFileHeader h{};
+    std::memcpy(h.magic, "VHCOLR01", 8);
+    h.numEntries = c->numEntries;
+    h.numVoxelBlocks = c->params.numVoxelBlocks;
+    for (const VoxelEntry &e : table) h.numAllocated += e.ptr != VH_FREE_BLOCK;
+    const std::string tmp = std::string(path) + ".partial";       // (renamed over the target at the end, as the snapshot is)
+    FILE *f = std::fopen(tmp.c_str(), "wb");
+    if (!f) return fail(VH_ERR_INVALID_ARGUMENT, "cannot open the colour file");
+    bool ok = std::fwrite(&h, sizeof h, 1, f) == 1;
+    DeviceGuard guard(c->device);
+    ColorFileRecord rec;
+    for (const VoxelEntry &e : table) {
+        if (e.ptr == VH_FREE_BLOCK || !ok) continue;
+        std::memcpy(rec.pos, e.pos, sizeof rec.pos);
+        if (hipMemcpy(rec.words, c->color.get() + e.ptr, sizeof rec.words, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; break; }
+        ok = std::fwrite(&rec, sizeof rec, 1, f) == 1;
+    }
+    ok = (std::fflush(f) == 0) && ok;
+    ok = (std::fclose(f) == 0) && ok;
+    if (ok) ok = std::rename(tmp.c_str(), path) == 0;
+    if (!ok) {
+        (void)std::remove(tmp.c_str());
+        return fail(VH_ERR_HIP, "colour file write failed");
+    }
+    return VH_OK;
+}
+
+// Everything is validated on the host before a device byte changes: the header against this context, the file size, and the
+// file's sequence of keys against the entries the context holds now, in table order.  Only the words are streamed afterwards;
+// should reading them fail then (an I/O error after the size check), the volume is left cleared rather than half-loaded.
+extern "C" int vh_load_color(vh_context *c, const char *path)
+{
+    if (!c || !path) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
+    if (c->viewBlocks) return fail(VH_ERR_INVALID_ARGUMENT, "a view table owns no blocks");
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return fail(VH_ERR_INVALID_ARGUMENT, "cannot open the colour file");
+    struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{f};
+    ColorFileHeader h;
+    if (std::fread(&h, sizeof h, 1, f) != 1 || std::memcmp(h.magic, "VHCOLR01", 8) != 0)
+        return fail(VH_ERR_INVALID_ARGUMENT, "not a colour file");
+    if (h.numEntries != c->numEntries || h.numVoxelBlocks != c->params.numVoxelBlocks)
+        return fail(VH_ERR_INVALID_ARGUMENT, "colour file does not match this context");
+    std::vector<VoxelEntry> table(c->numEntries);
+    int rc = vh_download(c, VH_BUF_HASH_TABLE, table.data(), table.size() * sizeof(VoxelEntry));     // (synchronises)
+    if (rc != VH_OK) return rc;
+    std::vector<int32_t> ptrs;
+    for (const VoxelEntry &e : table)
+        if (e.ptr != VH_FREE_BLOCK) ptrs.push_back(e.ptr);
+    if (h.numAllocated != ptrs.size()) return fail(VH_ERR_INVALID_ARGUMENT, "colour file belongs to another model: the block counts differ");
+    if (std::fseek(f, 0, SEEK_END) != 0) return fail(VH_ERR_INVALID_ARGUMENT, "colour file is unreadable");
+    const long file_end = std::ftell(f);
+    if (file_end < 0 || (uint64_t)file_end != sizeof h + h.numAllocated * sizeof(ColorFileRecord))
+        return fail(VH_ERR_INVALID_ARGUMENT, "colour file is truncated or has trailing bytes");
+    size_t at = 0;
+    for (const VoxelEntry &e : table) {
+        if (e.ptr == VH_FREE_BLOCK) continue;
+        int32_t pos[3];
+        if (std::fseek(f, (long)(sizeof h + at * sizeof(ColorFileRecord)), SEEK_SET) != 0 || std::fread(pos, sizeof pos, 1, f) != 1)
+            return fail(VH_ERR_INVALID_ARGUMENT, "colour file is unreadable");
+        if (std::memcmp(pos, e.pos, sizeof pos) != 0)
+            return fail(VH_ERR_INVALID_ARGUMENT, "colour file belongs to another model: its keys are not this table's");
+        ++at;
+    }
+    if (std::fseek(f, (long)sizeof h, SEEK_SET) != 0) return fail(VH_ERR_INVALID_ARGUMENT, "colour file is unreadable");
+
+    // ---- from here on the device state changes ----
+    DeviceGuard guard(c->device);
+    if ((rc = ensure_color(c)) != VH_OK) return rc;
+    hipError_t e = reset_color(c);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    ColorFileRecord rec;
+    bool ok = true;
+    for (size_t i = 0; ok && e == hipSuccess && i < ptrs.size(); ++i) {
+        ok = std::fread(&rec, sizeof rec, 1, f) == 1;
+        if (ok) e = hipMemcpy(c->color.get() + ptrs[i], rec.words, sizeof rec.words, hipMemcpyHostToDevice);
+    }
+    if (!ok || e != hipSuccess) {
+        (void)reset_color(c);                        // never leave a half-loaded volume behind
+        (void)hipStreamSynchronize(c->stream);
+        return !ok ? fail(VH_ERR_INVALID_ARGUMENT, "colour file could not be read; the colour volume was cleared")
+                   : fail(VH_ERR_HIP, "colour upload failed; the colour volume was cleared", e);
+    }
+    return VH_OK;
 }
 
 extern "C" int vh_has_color(vh_context *c) { return c && c->color ? 1 : 0; }

@@ -1,6 +1,6 @@
-// vh_api_merge.hip -- C-ABI, one model fused into another under a rigid transform: vh_merge (kernels: vh_merge.hip).
-// Included by vh_api.hip (same translation unit: shares fail(), VH_HIP, DeviceGuard, launch(), flush_pending(), settle(),
-// ensure_candidates(), invert4x4(), bin_parts()).
+// vh_api_merge.hip -- C-ABI, one model fused into another under a rigid transform: vh_merge, vh_merge_color (kernels:
+// vh_merge.hip).  Included by vh_api.hip (same translation unit: shares fail(), VH_HIP, DeviceGuard, launch(), flush_pending(),
+// settle(), ensure_candidates(), invert4x4(), bin_parts(), ensure_color()).
 // The call reads counters back between its allocation rounds and for its stats: it synchronises dst's stream.
 
 // The candidate records a call is willing to hold: 2^24 of 16 bytes, 256 MiB of scratch.  A source block gives (about) 8 to 27
@@ -15,9 +15,11 @@ static int merge_read(vh_context *c, unsigned long long words[kMergeWords], int3
     return VH_OK;
 }
 
-extern "C" int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst[16], int32_t mode, vh_merge_stats *stats)
+// colorWeightMax == 0: vh_merge.  1..255: vh_merge_color -- the same call with the colour step in its update launch, where src
+// has colour to give.
+static int merge_impl(vh_context *dst, vh_context *src, const float src_to_dst[16], int32_t mode, int32_t colorWeightMax,
+                      vh_merge_stats *stats)
 {
-    VH_TRACE("vh_merge");
     if (!dst || !src || !src_to_dst) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
     if (src == dst) return fail(VH_ERR_INVALID_ARGUMENT, "a model cannot be merged into itself");
     if (src->device != dst->device) return fail(VH_ERR_INVALID_ARGUMENT, "the two contexts live on different devices");
@@ -35,7 +37,11 @@ extern "C" int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst
     if (stats) *stats = st;
 
     DeviceGuard guard(dst->device);
-    int rc = flush_pending(src);                     // a pending pipelined frame of either context is part of its model
+    // a src without colour (a view table's records carry none) has none to give: the call is vh_merge
+    const bool colored = colorWeightMax > 0 && src->color && !src->viewBlocks;
+    int rc = colored ? ensure_color(dst) : VH_OK;    // (before anything else changes)
+    if (rc != VH_OK) return rc;
+    rc = flush_pending(src);                         // a pending pipelined frame of either context is part of its model
     if (rc == VH_OK) rc = settle(dst);
     if (rc != VH_OK) return rc;
     MergeScratch &ms = dst->merge;
@@ -105,9 +111,20 @@ extern "C" int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst
     DevPtrs srcDp = src->dp;
     if (src->viewBlocks) srcDp.blocks = const_cast<Voxel *>(src->viewBlocks);     // view table: voxels live in the records
     const dim3 grid((unsigned)dst->integrateGrid);
-    rc = mode == VH_SAMPLE_NEAREST
-             ? launch(dst, kPhaseIntegrate, merge_update_kernel<kSampleNearest>, grid, dim3(256), dst->fp, dst->dp, src->fp, srcDp, Tinv)
-             : launch(dst, kPhaseIntegrate, merge_update_kernel<kSampleTrilinear>, grid, dim3(256), dst->fp, dst->dp, src->fp, srcDp, Tinv);
+    if (colored) {
+        uint32_t *dstColor = dst->color.get();
+        const uint32_t *srcColor = src->color.get();
+        const uint32_t cap = (uint32_t)colorWeightMax;
+        rc = mode == VH_SAMPLE_NEAREST
+                 ? launch(dst, kPhaseIntegrate, merge_color_update_kernel<kSampleNearest>, grid, dim3(256), dst->fp, dst->dp, dstColor,
+                          src->fp, srcDp, srcColor, Tinv, cap)
+                 : launch(dst, kPhaseIntegrate, merge_color_update_kernel<kSampleTrilinear>, grid, dim3(256), dst->fp, dst->dp, dstColor,
+                          src->fp, srcDp, srcColor, Tinv, cap);
+    } else {
+        rc = mode == VH_SAMPLE_NEAREST
+                 ? launch(dst, kPhaseIntegrate, merge_update_kernel<kSampleNearest>, grid, dim3(256), dst->fp, dst->dp, src->fp, srcDp, Tinv)
+                 : launch(dst, kPhaseIntegrate, merge_update_kernel<kSampleTrilinear>, grid, dim3(256), dst->fp, dst->dp, src->fp, srcDp, Tinv);
+    }
     if (rc != VH_OK) return rc;
     VH_HIP(hipMemsetAsync(dst->dp.gcMarks, 0, sizeof(uint32_t) * ((dst->numEntries + 31) / 32), dst->stream));
     int32_t occupied = 0;
@@ -118,4 +135,18 @@ extern "C" int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst
     dst->params.numOccupiedBlocks = (uint32_t)occupied;
     if (stats) *stats = st;
     return VH_OK;
+}
+
+extern "C" int vh_merge(vh_context *dst, vh_context *src, const float src_to_dst[16], int32_t mode, vh_merge_stats *stats)
+{
+    VH_TRACE("vh_merge");
+    return merge_impl(dst, src, src_to_dst, mode, 0, stats);
+}
+
+extern "C" int vh_merge_color(vh_context *dst, vh_context *src, const float src_to_dst[16], int32_t mode, int32_t weight_max,
+                              vh_merge_stats *stats)
+{
+    VH_TRACE("vh_merge_color");
+    if (weight_max < 1 || weight_max > 255) return fail(VH_ERR_INVALID_ARGUMENT, "weight_max must be 1..255");
+    return merge_impl(dst, src, src_to_dst, mode, weight_max, stats);
 }

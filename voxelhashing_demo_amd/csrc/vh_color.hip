@@ -9,6 +9,7 @@
 //   color_integrate_kernel   the TSDF update's launch shape: 256 lanes own one 8^3 block per pass, lane t voxels 2t and 2t + 1;
 //                            one 16-byte load of the TSDF pair (read only), one 8-byte load of the colour pair, one 4-byte
 //                            gather per voxel from the image, one 8-byte store when a word changed
+//   color_deintegrate_kernel the same launch with the sample taken back out of the running average (vh_deintegrate_color)
 //   color_release_kernel     the colour words of the blocks a deletion freed, zeroed (ahead of gc_release_kernel, same list)
 //   color_points_kernel      one point per lane, the run-sharing look-ups of sample_points_kernel
 #pragma once
@@ -17,8 +18,11 @@ namespace vh {
 
 // The frame's colour sample of voxel (vx, vy, vz) combined into its word c; ow is the voxel's stored TSDF weight.
 // true: the word changed.  The camera point, the projection, the bounds test and the depth read are tsdf_apply's
-// (vh_integrate.hip), stated a second time so that the kernels of the TSDF update keep their code.
-template <class Depth>
+// (vh_integrate.hip), stated a second time so that the kernels of the TSDF update keep their code.  Two compile-time tails, as
+// tsdf_apply has them: kColorAdd averages the pixel in, kColorRemove takes it back out (vh_deintegrate_color; weightMax unused).
+enum ColorOp { kColorAdd, kColorRemove };
+
+template <ColorOp kOp, class Depth>
 __device__ __forceinline__ bool color_apply(const FrameParams &fp, const Depth &src, const uint32_t *__restrict__ rgba, float band,
                                             uint32_t weightMax, int vx, int vy, int vz, float ow, uint32_t &c)
 {
@@ -44,6 +48,22 @@ __device__ __forceinline__ bool color_apply(const FrameParams &fp, const Depth &
     if (depth <= 0.0f) return false;
     const float s = depth - cz;             // no truncation: colour belongs to the surface
     if (!(__builtin_fabsf(s) <= band)) return false;
+    if constexpr (kOp == kColorRemove) {
+        const uint32_t w = c >> 24;
+        if (w == 0u) return false;          // nothing to take out
+        if (w == 1u) { c = 0u; return true; }
+        const uint32_t in = rgba[(size_t)sy * fp.width + sx];
+        const float fw = (float)w, den = (float)(w - 1u);
+        uint32_t out = (w - 1u) << 24;
+#pragma unroll
+        for (int k = 0; k < 24; k += 8) {
+            float f = ((float)((c >> k) & 255u) * fw - (float)((in >> k) & 255u)) / den;
+            f = __builtin_fminf(__builtin_fmaxf(f, 0.0f), 255.0f);      // (the stored mean was rounded: the inverse may leave a byte)
+            out |= (uint32_t)(f + 0.5f) << k;
+        }
+        c = out;                            // (the count moved: the word changed)
+        return true;
+    }
     if (weightMax == 0u) return false;      // the sweep only
     const uint32_t in = rgba[(size_t)sy * fp.width + sx];
     const uint32_t w = c >> 24;
@@ -73,8 +93,28 @@ __global__ __launch_bounds__(256) void color_integrate_kernel(const FrameParams 
         const float4 v = *cell.cell;                                                        // {sdf0, w0, sdf1, w1}
         uint2 *words = reinterpret_cast<uint2 *>(color + (size_t)e.ptr + 2 * threadIdx.x);
         uint2 c = *words;
-        const bool u0 = color_apply(fp, src, rgba, band, weightMax, cell.bx, cell.by, cell.bz, v.y, c.x);
-        const bool u1 = color_apply(fp, src, rgba, band, weightMax, cell.bx + 1, cell.by, cell.bz, v.w, c.y);
+        const bool u0 = color_apply<kColorAdd>(fp, src, rgba, band, weightMax, cell.bx, cell.by, cell.bz, v.y, c.x);
+        const bool u1 = color_apply<kColorAdd>(fp, src, rgba, band, weightMax, cell.bx + 1, cell.by, cell.bz, v.w, c.y);
+        if (u0 || u1) *words = c;
+    }
+}
+
+// The same grid over the list the flatten left for the frame's pose, the frame's colour sample taken back out of every word
+// that passes color_apply's tests (the TSDF is read as it stands: the call goes ahead of the frame's vh_deintegrate_depth).
+template <class Depth>
+__global__ __launch_bounds__(256) void color_deintegrate_kernel(const FrameParams fp, const DevPtrs dp, const Depth src,
+                                                                uint32_t *__restrict__ color, const uint32_t *__restrict__ rgba,
+                                                                float band)
+{
+    const int count = dp.counters[kCompactCount];
+    for (int k = blockIdx.x; k < count; k += gridDim.x) {
+        const VoxelEntry e = dp.compact[k];
+        const LaneCell cell = lane_cell(dp, e);
+        const float4 v = *cell.cell;                                                        // {sdf0, w0, sdf1, w1}
+        uint2 *words = reinterpret_cast<uint2 *>(color + (size_t)e.ptr + 2 * threadIdx.x);
+        uint2 c = *words;
+        const bool u0 = color_apply<kColorRemove>(fp, src, rgba, band, 0u, cell.bx, cell.by, cell.bz, v.y, c.x);
+        const bool u1 = color_apply<kColorRemove>(fp, src, rgba, band, 0u, cell.bx + 1, cell.by, cell.bz, v.w, c.y);
         if (u0 || u1) *words = c;
     }
 }

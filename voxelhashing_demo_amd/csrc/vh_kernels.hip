@@ -29,10 +29,10 @@
 //                      its gradient as normal (no counterpart in the reference)
 //   vh_merge.hip       one model fused into another under a rigid transform: candidate keys from the source's blocks through the
 //                      bin insertion path, then the TSDF update's launch shape with the distance-field sample as the measurement
-//                      (no counterpart in the reference)
+//                      (no counterpart in the reference); the same launch with src's colour carried along (vh_merge_color)
 //   vh_color.hip       the model in colour: a second volume of one word per voxel, the registered colour image fused into the
-//                      voxels near the surface in the TSDF update's launch shape, colour at world points with the sampler's
-//                      shared look-ups (no counterpart in the reference)
+//                      voxels near the surface in the TSDF update's launch shape and taken back out of them, colour at world
+//                      points with the sampler's shared look-ups (no counterpart in the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one

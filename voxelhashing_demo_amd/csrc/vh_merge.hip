@@ -8,6 +8,8 @@
 //   merge_list_kernel      the distinct blocks of the bin that dst holds, each once into the compact list (one mark bit per entry)
 //   merge_update_kernel    the TSDF update's launch shape over that list: a 256-lane workgroup per 8^3 block, two x-neighbouring
 //                          voxels per lane as one 16-byte cell, each sampled from src by sample_trilinear / the nearest sample
+//   merge_color_update_kernel   the same launch with the colour step in it (vh_merge_color): the sample's blocks
+//                          resolved once, both of src's volumes read through those pointers, the colour pair one 8-byte cell
 #pragma once
 
 namespace vh {
@@ -204,6 +206,190 @@ __global__ __launch_bounds__(256) void merge_update_kernel(const FrameParams dst
         const bool u0 = merge_voxel<kMode>(dst, src, srcDp, Tinv, lane, c.bx, c.by, c.bz, v.x, v.y);
         const bool u1 = merge_voxel<kMode>(dst, src, srcDp, Tinv, lane, c.bx + 1, c.by, c.bz, v.z, v.w);
         if (u0 || u1) *c.cell = v;
+    }
+}
+
+// ---- geometry and colour in one launch: vh_merge_color (the rule: include/voxelhash.h, tests/merge_color_ref.py) ----
+// The sample's source blocks are resolved once and both of src's volumes are read through those pointers: the TSDF sample is
+// merge_voxel's (the same bits), the colour sample reads the words beside the voxels it used.  The colour volumes are no
+// members of DevPtrs (vh_color.hip): they travel as kernel arguments.
+
+// src's colour sample combined into dst's word c; wIn > 0
+__device__ __forceinline__ uint32_t merge_color_word(uint32_t c, uint32_t rgb, uint32_t wIn, uint32_t weightMax)
+{
+    const uint32_t wd = c >> 24;
+    if (wd == 0u) return rgb | (min(wIn, weightMax) << 24);
+    const float fd = (float)wd, fs = (float)wIn, den = (float)(wd + wIn);
+    uint32_t out = min(wd + wIn, weightMax) << 24;
+#pragma unroll
+    for (int k = 0; k < 24; k += 8) {
+        const float f = ((float)((c >> k) & 255u) * fd + (float)((rgb >> k) & 255u) * fs) / den;
+        out |= (uint32_t)(f + 0.5f) << k;       // (at most 255: a weighted mean of bytes)
+    }
+    return out;
+}
+
+// The VH_SAMPLE_TRILINEAR sdf, weight and colour at u.  The corner walk and the two lerp nests are sample_trilinear's
+// (vh_sample.hip), restated because the colour words need the corners' block pointers; the channels go one at a time over the
+// eight words so that no more than those stay live.  count == 0: no colour sample.  Called by every lane of the wave.
+struct MergeColorSample { float sdf, weight; uint32_t rgb, count; };
+
+__device__ __forceinline__ MergeColorSample merge_color_trilinear(const FrameParams &fp, const DevPtrs &dp,
+                                                                  const uint32_t *__restrict__ color, int lane, const float u[3],
+                                                                  bool inDomain)
+{
+    const float nan = __builtin_nanf("");
+    MergeColorSample r = {nan, 0.0f, 0u, 0u};
+    int i[3] = {0, 0, 0};
+    float t[3] = {0.0f, 0.0f, 0.0f};
+    if (inDomain) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float f = __builtin_floorf(u[a]);
+            i[a] = f2i_rz(f);
+            t[a] = u[a] - f;
+        }
+    }
+    const int kx = i[0] >> 3, ky = i[1] >> 3, kz = i[2] >> 3;
+    const int cross = ((i[0] & 7) == 7 ? 1 : 0) | ((i[1] & 7) == 7 ? 2 : 0) | ((i[2] & 7) == 7 ? 4 : 0);
+    const SampleRuns runs = sample_runs(lane, kx, ky, kz);
+    int ptr[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int p = sample_resolve(fp, dp, lane, runs, inDomain && (c & ~cross) == 0, kx + (c & 1), ky + ((c >> 1) & 1),
+                                     kz + (c >> 2));
+        if ((c & ~cross) == 0) ptr[c] = p;
+        else if (c & ~cross & 1) ptr[c] = ptr[c & 6];
+        else if (c & ~cross & 2) ptr[c] = ptr[c & 5];
+        else ptr[c] = ptr[c & 3];
+    }
+    SampleVoxel v[8];
+#pragma unroll
+    for (int c = 0; c < 8; c += 2) {
+        const int index = sample_index(i[0], i[1] + ((c >> 1) & 1), i[2] + (c >> 2));
+        if (!(cross & 1)) {
+            v[c] = v[c + 1] = SampleVoxel{nan, 0.0f};
+            if (ptr[c] != VH_FREE_BLOCK) {
+                const VoxelPair pair = *reinterpret_cast<const VoxelPair *>(dp.blocks + (size_t)ptr[c] + (size_t)index);
+                v[c] = sample_judge(pair.s0, pair.w0);
+                v[c + 1] = sample_judge(pair.s1, pair.w1);
+            }
+        } else {
+            v[c] = sample_voxel(dp, ptr[c], index);
+            v[c + 1] = sample_voxel(dp, ptr[c + 1], sample_index(i[0] + 1, i[1] + ((c >> 1) & 1), i[2] + (c >> 2)));
+        }
+    }
+    bool all = inDomain;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) all = all && v[c].sdf == v[c].sdf;
+    if (!all) return r;
+    const float tx = t[0], ty = t[1], tz = t[2];
+    r.sdf = sample_lerp(sample_lerp(sample_lerp(v[0].sdf, v[1].sdf, tx), sample_lerp(v[2].sdf, v[3].sdf, tx), ty),
+                        sample_lerp(sample_lerp(v[4].sdf, v[5].sdf, tx), sample_lerp(v[6].sdf, v[7].sdf, tx), ty), tz);
+    r.weight = sample_lerp(sample_lerp(sample_lerp(v[0].weight, v[1].weight, tx), sample_lerp(v[2].weight, v[3].weight, tx), ty),
+                           sample_lerp(sample_lerp(v[4].weight, v[5].weight, tx), sample_lerp(v[6].weight, v[7].weight, tx), ty), tz);
+    if (!(r.weight > 0.0f)) return r;           // (no TSDF step, so no colour step: the words are not read)
+    // eight valid corners: every ptr names a block, inside src's colour volume as it is inside its SDF volume
+    uint32_t w[8], least = 255u;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        w[c] = color[(size_t)ptr[c] + (size_t)sample_index(i[0] + (c & 1), i[1] + ((c >> 1) & 1), i[2] + (c >> 2))];
+        least = min(least, w[c] >> 24);
+    }
+    if (least == 0u) return r;
+    r.count = least;
+#pragma unroll
+    for (int k = 0; k < 24; k += 8) {
+        float s[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) s[c] = (float)((w[c] >> k) & 255u);
+        const float f = sample_lerp(sample_lerp(sample_lerp(s[0], s[1], tx), sample_lerp(s[2], s[3], tx), ty),
+                                    sample_lerp(sample_lerp(s[4], s[5], tx), sample_lerp(s[6], s[7], tx), ty), tz);
+        r.rgb |= (uint32_t)(f + 0.5f) << k;
+    }
+    return r;
+}
+
+// the VH_SAMPLE_NEAREST form: merge_sample_nearest with the word beside the voxel
+__device__ __forceinline__ MergeColorSample merge_color_nearest(const FrameParams &fp, const DevPtrs &dp,
+                                                                const uint32_t *__restrict__ color, int lane, const float u[3],
+                                                                bool inDomain)
+{
+    int r[3] = {0, 0, 0};
+    if (inDomain) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) r[a] = f2i_rz(u[a] + __builtin_copysignf(0.5f, u[a]));
+    }
+    const int kx = r[0] >> 3, ky = r[1] >> 3, kz = r[2] >> 3;
+    const SampleRuns runs = sample_runs(lane, kx, ky, kz);
+    const int resolved = sample_resolve(fp, dp, lane, runs, inDomain, kx, ky, kz);
+    const int ptr = inDomain ? resolved : VH_FREE_BLOCK;
+    const int index = sample_index(r[0], r[1], r[2]);
+    const SampleVoxel v = sample_voxel(dp, ptr, index);
+    MergeColorSample out = {v.sdf, v.weight, 0u, 0u};
+    if (v.sdf == v.sdf) {                       // (a valid voxel: ptr names a block)
+        const uint32_t word = color[(size_t)ptr + (size_t)index];
+        out.rgb = word & 0xffffffu;
+        out.count = word >> 24;
+    }
+    return out;
+}
+
+// merge_voxel with the colour step behind it: bit 0 = the voxel changed, bit 1 = the word did
+template <int kMode>
+__device__ __forceinline__ int merge_color_voxel(const FrameParams &dst, const FrameParams &src, const DevPtrs &srcDp,
+                                                 const uint32_t *__restrict__ srcColor, const MergeTransform &Tinv, int lane,
+                                                 uint32_t weightMax, int gx, int gy, int gz, float &sdfIO, float &wIO, uint32_t &cIO)
+{
+    const float px = (float)gx * dst.voxelSize, py = (float)gy * dst.voxelSize, pz = (float)gz * dst.voxelSize;
+    float u[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) u[r] = merge_row(Tinv.m, r, px, py, pz) / src.voxelSize;
+    const bool inDomain = __builtin_fabsf(u[0]) < kSampleDomain && __builtin_fabsf(u[1]) < kSampleDomain &&
+                          __builtin_fabsf(u[2]) < kSampleDomain;          // false for NaN
+    MergeColorSample v;
+    if constexpr (kMode == kSampleNearest) v = merge_color_nearest(src, srcDp, srcColor, lane, u, inDomain);
+    else v = merge_color_trilinear(src, srcDp, srcColor, lane, u, inDomain);
+    float s = v.sdf;
+    const float w = v.weight;
+    if (!(s == s) || !(w > 0.0f)) return 0;
+    s = (s >= 0.0f) ? __builtin_fminf(dst.truncation, s) : __builtin_fmaxf(-dst.truncation, s);
+    const float os = sdfIO, ow = wIO;
+    if (!(ow > 0.0f)) {
+        sdfIO = s;
+        wIO = __builtin_fminf(dst.weightMax, w);
+    } else {
+        sdfIO = ((os * ow) + (s * w)) / (ow + w);                       // combineVoxel's form
+        wIO = __builtin_fminf(dst.weightMax, ow + w);
+    }
+    if (v.count == 0u) return 1;
+    const uint32_t c = merge_color_word(cIO, v.rgb, v.count, weightMax);
+    const int changed = c != cIO ? 3 : 1;
+    cIO = c;
+    return changed;
+}
+
+// merge_update_kernel's shape: one block of dst's compact list per workgroup pass, lane t voxels 2t and 2t + 1 -- the TSDF pair
+// one 16-byte load and store, the colour pair one 8-byte load and store, each stored only when something in it changed.  No
+// lane leaves before the samples' cross-lane reads.  src's two volumes are only read.
+template <int kMode>
+__global__ __launch_bounds__(256) void merge_color_update_kernel(const FrameParams dst, const DevPtrs dstDp, uint32_t *__restrict__ dstColor,
+                                                                 const FrameParams src, const DevPtrs srcDp,
+                                                                 const uint32_t *__restrict__ srcColor, const MergeTransform Tinv,
+                                                                 uint32_t weightMax)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const int count = dstDp.counters[kCompactCount];
+    for (int k = (int)blockIdx.x; k < count; k += (int)gridDim.x) {
+        const VoxelEntry e = dstDp.compact[k];
+        const LaneCell c = lane_cell(dstDp, e);
+        float4 v = *c.cell;
+        uint2 *words = reinterpret_cast<uint2 *>(dstColor + (size_t)e.ptr + 2 * threadIdx.x);
+        uint2 w = *words;
+        const int u0 = merge_color_voxel<kMode>(dst, src, srcDp, srcColor, Tinv, lane, weightMax, c.bx, c.by, c.bz, v.x, v.y, w.x);
+        const int u1 = merge_color_voxel<kMode>(dst, src, srcDp, srcColor, Tinv, lane, weightMax, c.bx + 1, c.by, c.bz, v.z, v.w, w.y);
+        if ((u0 | u1) & 1) *c.cell = v;
+        if ((u0 | u1) & 2) *words = w;
     }
 }
 

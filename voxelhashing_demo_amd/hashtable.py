@@ -199,16 +199,20 @@ class SDFHashtable:
                 "vh_reintegrate_depth")
 
     # ---- one model into another ----
-    def merge(self, src, src_to_dst, mode: int = L.SAMPLE_TRILINEAR) -> dict:
+    def merge(self, src, src_to_dst, mode: int = L.SAMPLE_TRILINEAR, colors: bool = False, color_weight_max: int = 255) -> dict:
         """vh_merge: the model of `src` (another SDFHashtable on this device) fused into this one under the rigid 4x4
         src_to_dst (src world metres -> this model's).  Voxel sizes may differ.  Synchronises this context's stream; src is only
         read.  Returns vh_merge_stats as a dict; garbage_collect() directly afterwards frees the candidate blocks that stayed
-        empty."""
+        empty.  colors=True is vh_merge_color: the same call with src's colour carried along in the same launch
+        (color_weight_max: 1..255, the cap of the merged sample counts); a src without colour gives exactly the plain merge."""
         if not isinstance(src, SDFHashtable):
             raise TypeError("merge: src must be an SDFHashtable")
         _, pp = _pose16(src_to_dst)
         st = L.MergeStats()
-        L.check(self._lib.vh_merge(self._h, src._h, pp, int(mode), C.byref(st)), "vh_merge")
+        if colors:
+            L.check(self._lib.vh_merge_color(self._h, src._h, pp, int(mode), int(color_weight_max), C.byref(st)), "vh_merge_color")
+        else:
+            L.check(self._lib.vh_merge(self._h, src._h, pp, int(mode), C.byref(st)), "vh_merge")
         return st.as_dict()
 
     # ---- the model in colour (DESIGN.md 4.14) ----
@@ -249,6 +253,45 @@ class SDFHashtable:
         k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
         L.check(self._lib.vh_integrate_depth_color(self._h, pp, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float)),
                                                    _dev_ptr(rgba), float(band), int(weight_max)), "vh_integrate_depth_color")
+
+    # ---- colour through de-integration and saved models ----
+    def deintegrate_color(self, pose, depth_u16, k_inv, rgba, band: float):
+        """Asynchronous: the colour sample integrate_color(pose, ...) added taken back out of the running averages (the exact
+        inverse only below the colour cap, up to byte rounding).  Call it before the frame's deintegrate_depth."""
+        _, pp = _pose16(pose)
+        self._check_depth_u16(depth_u16, "deintegrate_color")
+        self._check_rgba(rgba, "deintegrate_color")
+        k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        L.check(self._lib.vh_deintegrate_color(self._h, pp, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                               _dev_ptr(rgba), float(band)), "vh_deintegrate_color")
+
+    def deintegrate_depth_color(self, pose, depth_u16, k_inv, rgba, band: float):
+        """One RGB-D frame taken back out: deintegrate_color, deintegrate_depth, then the sweep of the voxels that emptied."""
+        _, pp = _pose16(pose)
+        self._check_depth_u16(depth_u16, "deintegrate_depth_color")
+        self._check_rgba(rgba, "deintegrate_depth_color")
+        k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        L.check(self._lib.vh_deintegrate_depth_color(self._h, pp, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                                     _dev_ptr(rgba), float(band)), "vh_deintegrate_depth_color")
+
+    def reintegrate_depth_color(self, old_pose, new_pose, depth_u16, k_inv, rgba, band: float, weight_max: int = 255):
+        """deintegrate_depth_color(old_pose) + integrate_depth_color(new_pose): an RGB-D frame moved to its corrected pose."""
+        _, po = _pose16(old_pose)
+        _, pn = _pose16(new_pose)
+        self._check_depth_u16(depth_u16, "reintegrate_depth_color")
+        self._check_rgba(rgba, "reintegrate_depth_color")
+        k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        L.check(self._lib.vh_reintegrate_depth_color(self._h, po, pn, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                                     _dev_ptr(rgba), float(band), int(weight_max)), "vh_reintegrate_depth_color")
+
+    def save_color(self, path: str):
+        """The colour words of the allocated blocks as a file beside a snapshot (save_snapshot + save_color)."""
+        L.check(self._lib.vh_save_color(self._h, str(path).encode()), "vh_save_color")
+
+    def load_color(self, path: str):
+        """Restores save_color's file into the model as it is now: call it after load_snapshot.  A file that does not match
+        the model's blocks is refused and nothing changes."""
+        L.check(self._lib.vh_load_color(self._h, str(path).encode()), "vh_load_color")
 
     def has_color(self) -> bool:
         return bool(self._lib.vh_has_color(self._h))
