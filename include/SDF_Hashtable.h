@@ -136,6 +136,13 @@ public:
                                const uint32_t *d_rgba, float band, int weightMax = 255);
     void saveColor(const char *path);
     void loadColor(const char *path);
+    /* Block streaming (vh_stream_out_host / vh_stream_in_host, voxelhash.h "block streaming"): streamOut takes every allocated
+     * block of `region` out of the model into `records` (key + 512 voxels each, in entry order) and, with `colors`, their 512
+     * colour words each -- without it the colour of those blocks is dropped; returns the number of blocks moved.  streamIn puts
+     * records back: colors (optional) 512 words per record, status (optional) one VH_STREAM_* per record.  Both synchronise. */
+    uint64_t streamOut(const vh_stream_region &region, std::vector<vh_view_record> &records, std::vector<uint32_t> *colors = nullptr);
+    void streamIn(const std::vector<vh_view_record> &records, const std::vector<uint32_t> *colors = nullptr,
+                  std::vector<int32_t> *status = nullptr, vh_stream_stats *stats = nullptr);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

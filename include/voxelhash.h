@@ -158,8 +158,8 @@ typedef struct vh_kernel_times {
     uint64_t raycast_launches;
     double   frame_scan_claim_ms;        /* fused vh_integrate, launch 1: claim || table walk */
     double   frame_commit_integrate_ms;  /* fused vh_integrate, launch 2: commit + TSDF update */
-    double   view_export_ms;             /* vh_export_views: select walk + record packing */
-    double   view_import_ms;             /* vh_import_view: clear + insert */
+    double   view_export_ms;             /* vh_export_views: select walk + record packing; vh_stream_out: its pack launch */
+    double   view_import_ms;             /* vh_import_view: clear + insert; vh_stream_in: its place launch */
     double   gc_ms;                      /* vh_delete_blocks / vh_garbage_collect, all launches */
     uint64_t gc_calls;
     double   render_blocks_ms;           /* vh_render_blocks, all launches */
@@ -999,6 +999,75 @@ int vh_reintegrate_depth_color(vh_context *ctx, const float old_pose[16], const 
                                const float k_inv[9], const uint32_t *d_rgba, float band, int32_t weight_max);
 int vh_save_color(vh_context *ctx, const char *path);
 int vh_load_color(vh_context *ctx, const char *path);
+
+/* ------------------------------------------------------------------ */
+/* block streaming: a model larger than the block pool                 */
+/* ------------------------------------------------------------------ */
+/* Niessner et al. 2013, section 5: blocks that leave an active region around the camera move to the host and their pool slots
+ * are freed; they move back when the camera returns.  Two exact, lossless calls: vh_stream_out takes the blocks of a region out
+ * of the model as records, vh_stream_in puts records back.  The policy on top (which region, where the records are kept) is the
+ * caller's; voxelhashing_demo_amd/streaming.py has one.  No counterpart in the reference.
+ *
+ * The region.  VH_STREAM_BOX: the blocks with block_lo <= key < block_hi on every axis (bounds may be any int32).
+ * VH_STREAM_SPHERE: the blocks whose centre lies within `radius` of `centre` (world metres), float32, every operation rounded on
+ * its own, in exactly this order:
+ *     x_a = ((float)(8 * key_a) + 3.5f) * voxelSize - centre_a     for a = 0, 1, 2
+ *     d2  = (x_0 * x_0 + x_1 * x_1) + x_2 * x_2
+ *     inside iff d2 <= radius * radius
+ * invert = 1 selects the complement: everything OUTSIDE the box or sphere (what leaves an active region).  Key domain: that of the
+ * mesh, |key| < 2^28 on every axis.  radius must be finite and >= 0 and centre finite, kind one of the two: otherwise
+ * VH_ERR_INVALID_ARGUMENT and nothing changes.  A box does not use centre and radius (they are still checked: zeros will do), a
+ * sphere does not use block_lo and block_hi.
+ *
+ * vh_stream_out runs on the context's stream behind every frame queued so far (a pending pipelined frame is launched first) and
+ * synchronises to return its two counts (host): *selected_out = the allocated blocks the region holds, *written_out =
+ * min(selected, capacity).  The first `written` of them in ascending entry index of the hash table (the order of the mesh's block
+ * list) are written to d_records (capacity records, 16-byte aligned): {pos, reserved = 0, voxels[512]}, exactly the bytes the
+ * block held.  With d_colors (capacity * 512 words) record i's 512 colour words go to d_colors[512 * i ...], zeros if the context
+ * has no colour volume; with d_colors == NULL THE COLOUR OF THE REMOVED BLOCKS IS DROPPED.  Exactly the written blocks are then
+ * removed as vh_delete_blocks removes them: a lock epoch of its own, voxels and colour words zeroed, the blocks back on the heap,
+ * the compact list left empty, vh_counters.last_freed / freed_total updated -- the table is what vh_delete_blocks on those keys
+ * leaves, slot for slot.  Blocks selected beyond the capacity stay in the model: call again.  capacity == 0 (buffers may be NULL)
+ * is the count-only call; it, and a call that selects nothing, change nothing.
+ *
+ * vh_stream_in puts n records (n <= 2^24; d_colors: n * 512 words or NULL = the blocks get no colour) into the model and reports
+ * per record (d_status: n int32 on the device, or NULL) and in total (stats, host, may be NULL):
+ *     VH_STREAM_FOREIGN   the key hashes outside this shard's bucket range
+ *     VH_STREAM_PRESENT   the model already holds the key -- its block is NOT touched (fusing a record into a block that exists
+ *                         is vh_import_view + vh_merge) -- or the key occurs more than once in the call and another record won
+ *     VH_STREAM_PLACED    a block was allocated and holds the record's 512 voxels (and colour words), whole
+ *     VH_STREAM_UNPLACED  bucket full or pool empty: nothing written for this record
+ * Exactly one of the records of equal keys is placed; which one is unspecified.  No record is half-written or silently lost:
+ * placed + present + unplaced + foreign == n.  With d_colors the colour volume is created first.  The keys that are neither
+ * foreign nor present go through the insertion path of vh_insert_bins as one key bin, one lock epoch per round, until none is
+ * missing or a round allocates nothing (stats->rounds; the call synchronises between rounds).  The compact list is left empty.
+ *
+ * Both calls work on shards and with "overflow_list"; view tables are refused (they own no blocks).  The _host forms take host
+ * buffers, stage through device scratch the context keeps, and copy once each way; vh_stream_out_host sizes the scratch from the
+ * count, so `capacity` may be generous. */
+#define VH_STREAM_BOX    0
+#define VH_STREAM_SPHERE 1
+typedef struct vh_stream_region {
+    int32_t kind;                       /* VH_STREAM_BOX | VH_STREAM_SPHERE */
+    int32_t invert;                     /* 1: the complement */
+    int32_t block_lo[3], block_hi[3];
+    float   centre[3], radius;          /* world metres */
+} vh_stream_region;
+
+#define VH_STREAM_PLACED   0
+#define VH_STREAM_PRESENT  1
+#define VH_STREAM_UNPLACED 2
+#define VH_STREAM_FOREIGN  3
+typedef struct vh_stream_stats { uint64_t placed, present, unplaced, foreign; uint32_t rounds; } vh_stream_stats;
+
+int vh_stream_out(vh_context *ctx, const vh_stream_region *region, uint64_t capacity, vh_view_record *d_records,
+                  uint32_t *d_colors /* capacity * 512 words or NULL */, uint64_t *selected_out, uint64_t *written_out);
+int vh_stream_in(vh_context *ctx, uint64_t n, const vh_view_record *d_records, const uint32_t *d_colors /* n * 512 words or NULL */,
+                 int32_t *d_status /* n or NULL */, vh_stream_stats *stats /* host, may be NULL */);
+int vh_stream_out_host(vh_context *ctx, const vh_stream_region *region, uint64_t capacity, vh_view_record *h_records,
+                       uint32_t *h_colors, uint64_t *selected_out, uint64_t *written_out);
+int vh_stream_in_host(vh_context *ctx, uint64_t n, const vh_view_record *h_records, const uint32_t *h_colors, int32_t *h_status,
+                      vh_stream_stats *stats);
 
 /* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */

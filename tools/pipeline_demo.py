@@ -7,8 +7,11 @@ stage and the drift against the true trajectory; --mesh writes the fused model a
 (welded by position on the host), --mesh-indexed the indexed mesh the GPU makes (one vertex per cell edge).  --color fuses a
 synthetic colour image with every frame (vh_integrate_color_map, a band of three voxels); --snapshot writes the model at the end
 (vh_save_snapshot) and, where the model is coloured, its colour words beside it as <path>.color (vh_save_color): the pair
-load_snapshot + load_color resumes from.
-tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--snapshot out.vhsnap]"""
+load_snapshot + load_color resumes from.  --stream-radius R keeps only the blocks within R metres of the camera on the GPU: after
+every frame a streaming.BlockStore moves the blocks beyond R to the host and those within 0.8 R back (vh_stream_out / vh_stream_in);
+at the end every stored block is streamed back in, so a mesh or snapshot holds the whole model.  R should exceed the depth range:
+a block the camera still sees beyond R is allocated again by the next frame and streamed out again, replacing its stored record.
+tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--snapshot out.vhsnap] [--stream-radius R]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -32,6 +35,10 @@ SNAPSHOT = None
 if "--snapshot" in argv:
     SNAPSHOT = argv[argv.index("--snapshot") + 1]
     del argv[argv.index("--snapshot"):argv.index("--snapshot") + 2]
+STREAM_RADIUS = None
+if "--stream-radius" in argv:
+    STREAM_RADIUS = float(argv[argv.index("--stream-radius") + 1])
+    del argv[argv.index("--stream-radius"):argv.index("--stream-radius") + 2]
 N = int(argv[0]) if argv else 60
 gt = synth.camera_loop(500)[200:200 + N]
 prims = synth.room_primitives()
@@ -48,6 +55,12 @@ verts, normals = torch.empty((H, W, 4), device="cuda"), torch.empty((H, W, 4), d
 tp, tn = torch.empty_like(verts), torch.empty_like(verts)
 ray = torch.empty((H, W), device="cuda")
 stage = dict(preprocess=0.0, raycast_target=0.0, align=0.0, integrate=0.0, collect=0.0)
+store = None
+if STREAM_RADIUS is not None:
+    from voxelhashing_demo_amd import streaming
+    store = streaming.BlockStore(table.params.voxelSize)
+    stage["stream"] = 0.0
+    streamed = dict(out=0, back=0, most=0)
 if COLOR:
     stage["color"] = 0.0
     BAND = 3.0 * table.params.voxelSize
@@ -82,6 +95,12 @@ with torch.cuda.stream(stream):
             timed("color", lambda: table.integrate_color_map(pose.astype(np.float32), verts, rgba[k], BAND))
         if k % 20 == 19:
             timed("collect", lambda: table.garbage_collect(0.5))
+        if store is not None:
+            moved = [None]
+            timed("stream", lambda: moved.__setitem__(0, store.update(table, pose[:3, 3], 0.8 * STREAM_RADIUS, STREAM_RADIUS)))
+            streamed["out"] += moved[0]["out"]
+            streamed["back"] += moved[0]["in"]
+            streamed["most"] = max(streamed["most"], moved[0]["stored"])
         errs.append(float(np.abs(pose[:3, 3] - np.asarray(gt[k], np.float64).reshape(4, 4)[:3, 3]).max()))
 travel = float(np.linalg.norm(np.asarray(gt[-1], np.float64).reshape(4, 4)[:3, 3] - np.asarray(gt[0], np.float64).reshape(4, 4)[:3, 3]))
 print(f"{N} frames, {travel:.2f} m between first and last camera, blocks {table.counters()['allocated_total']}")
@@ -89,6 +108,12 @@ for name, t in stage.items():
     n = N - 1 if name in ("raycast_target", "align") else (N // 20 if name == "collect" else N)
     print(f"  {name:15s} {1e6 * t / max(1, n):8.1f} us per call (host-timed, synchronised)")
 print(f"  drift: max {1e3 * max(errs):.2f} mm, final {1e3 * errs[-1]:.2f} mm")
+if store is not None:
+    with torch.cuda.stream(stream):
+        left = store.restore_all(table)
+    print(f"  streaming: radius {STREAM_RADIUS} m, {streamed['out']} blocks out and {streamed['back']} back during the loop, at most "
+          f"{streamed['most']} on the host; at the end {left['placed']} restored, {left['present']} met a block allocated again "
+          f"under their key meanwhile (kept in the store), {left['unplaced']} unplaced")
 if MESH:
     from voxelhashing_demo_amd import mesh_io
     with torch.cuda.stream(stream):

@@ -20,6 +20,8 @@ BUF_HASH_TABLE, BUF_COMPACT, BUF_SDF_BLOCKS, BUF_HEAP = 0, 1, 2, 3
 FREE_BLOCK = -1
 SAMPLE_NEAREST, SAMPLE_TRILINEAR = 0, 1
 RAY_HIT, RAY_MISS, RAY_REFUSED = 1, 0, -1          # the status word of vh_cast_rays' d_voxels
+STREAM_BOX, STREAM_SPHERE = 0, 1                   # vh_stream_region.kind
+STREAM_PLACED, STREAM_PRESENT, STREAM_UNPLACED, STREAM_FOREIGN = 0, 1, 2, 3       # the per-record status of vh_stream_in
 
 
 class HashTableParams(C.Structure):
@@ -82,6 +84,21 @@ class MergeStats(C.Structure):
     """vh_merge_stats."""
     _fields_ = [("source_blocks", C.c_uint32), ("skipped_blocks", C.c_uint32), ("candidates", C.c_uint64),
                 ("allocated", C.c_uint32), ("blocks", C.c_uint32), ("unplaced", C.c_uint64), ("rounds", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class StreamRegion(C.Structure):
+    """vh_stream_region: a box of block keys or a sphere around a world point, or (invert) the complement."""
+    _fields_ = [("kind", C.c_int32), ("invert", C.c_int32), ("block_lo", C.c_int32 * 3), ("block_hi", C.c_int32 * 3),
+                ("centre", C.c_float * 3), ("radius", C.c_float)]
+
+
+class StreamStats(C.Structure):
+    """vh_stream_stats."""
+    _fields_ = [("placed", C.c_uint64), ("present", C.c_uint64), ("unplaced", C.c_uint64), ("foreign", C.c_uint64),
+                ("rounds", C.c_uint32)]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -174,6 +191,11 @@ SIGNATURES = {
     "vh_reintegrate_depth_color": (C.c_int, [_vp, _fp, _fp, _vp, _fp, _vp, _f, _i32]),
     "vh_save_color": (C.c_int, [_vp, C.c_char_p]),
     "vh_load_color": (C.c_int, [_vp, C.c_char_p]),
+    "vh_stream_out": (C.c_int, [_vp, C.POINTER(StreamRegion), C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vh_stream_in": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, C.POINTER(StreamStats)]),
+    "vh_stream_out_host": (C.c_int, [_vp, C.POINTER(StreamRegion), C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)]),
+    "vh_stream_in_host": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, C.POINTER(StreamStats)]),
     "vh_sdf_build_system": (C.c_int, [_vp, _vp, _vp, _fp, _f, C.POINTER(IcpSystem)]),
     "vh_sdf_residuals": (C.c_int, [_vp, _vp, _vp, _fp, _f, _vp, _vp, _vp, C.POINTER(IcpSystem)]),
     "vh_sdf_align": (C.c_int, [_vp, _vp, _vp, _f, C.c_int32, C.POINTER(C.c_double), C.POINTER(IcpSystem), C.POINTER(C.c_int32)]),

@@ -239,6 +239,31 @@ void SDF_Hashtable::saveColor(const char *path) { check(vh_save_color(ctx_, path
 
 void SDF_Hashtable::loadColor(const char *path) { check(vh_load_color(ctx_, path), "loadColor"); }
 
+uint64_t SDF_Hashtable::streamOut(const vh_stream_region &region, std::vector<vh_view_record> &records, std::vector<uint32_t> *colors)
+{
+    uint64_t selected = 0, written = 0;
+    check(vh_stream_out_host(ctx_, &region, 0, nullptr, nullptr, &selected, &written), "streamOut");
+    records.resize((size_t)selected);
+    if (colors) colors->assign((size_t)selected * 512, 0u);
+    if (selected)
+        check(vh_stream_out_host(ctx_, &region, selected, records.data(), colors ? colors->data() : nullptr, &selected, &written), "streamOut");
+    records.resize((size_t)written);
+    if (colors) colors->resize((size_t)written * 512);
+    return written;
+}
+
+void SDF_Hashtable::streamIn(const std::vector<vh_view_record> &records, const std::vector<uint32_t> *colors, std::vector<int32_t> *status,
+                             vh_stream_stats *stats)
+{
+    if (colors && colors->size() != records.size() * 512) {
+        std::fprintf(stderr, "SDF_Hashtable: streamIn needs 512 colour words per record\n");
+        std::exit(EXIT_FAILURE);
+    }
+    if (status) status->assign(records.size(), 0);
+    check(vh_stream_in_host(ctx_, records.size(), records.data(), colors ? colors->data() : nullptr, status ? status->data() : nullptr,
+                            stats), "streamIn");
+}
+
 uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
 {
     std::vector<float> pos, nrm;

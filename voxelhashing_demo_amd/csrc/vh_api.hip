@@ -156,6 +156,15 @@ struct MergeScratch {
     ~MergeScratch() { if (ordered) (void)hipEventDestroy(ordered); }
 };
 
+// vh_stream_in / the _host forms of both streaming calls (vh_api_stream.hip): scratch of the first call, kept and grown on demand
+struct StreamScratch {
+    DevBuf<int32_t> status;                // per-record status of a vh_stream_in
+    DevBuf<unsigned long long> totals;     // its four totals, indexed by VH_STREAM_*
+    DevBuf<uint8_t> records;               // the _host forms: the records in device memory
+    DevBuf<uint32_t> colors;               // ... and their colour words
+    DevBuf<int32_t> hostStatus;            // vh_stream_in_host: the statuses on their way back
+};
+
 struct vh_context {
     HashTableParams params;
     FrameParams fp;
@@ -239,6 +248,7 @@ struct vh_context {
     DevBuf<unsigned long long> meshVertexTotals;   // the vertex scan's tile totals, then {listed blocks, vertices, triangles}
     MergeScratch merge;                    // vh_merge into this context: scratch of its first call, kept
     DevBuf<uint32_t> color;                // the colour volume (vh_api_color.hip): one word per voxel, of the first colour-fusing call, kept
+    StreamScratch streaming;               // vh_stream_in, vh_stream_*_host: scratch of the first call, kept
 };
 
 struct DeviceGuard {
@@ -597,3 +607,4 @@ static int ensure_candidates(vh_context *c, size_t need)
 #include "vh_api_icp.hip"
 #include "vh_api_track.hip"
 #include "vh_api_dist.hip"
+#include "vh_api_stream.hip"

@@ -15,6 +15,34 @@ static int merge_read(vh_context *c, unsigned long long words[kMergeWords], int3
     return VH_OK;
 }
 
+// The allocation rounds of one key bin of `records` records (vh_merge, vh_stream_in): the bin goes through the claim + commit path,
+// one lock epoch per round, until nothing is missing or a round allocates nothing (buckets full, heap empty).  Every round that
+// goes on has allocated a block, so the heap bounds the loop.  words[kMergeMissing]: the records still missing at the end.
+static int bin_alloc_rounds(vh_context *dst, const int4 *bin, int32_t records, int32_t allocatedBefore,
+                            unsigned long long words[kMergeWords], int32_t *allocatedNow, uint32_t *rounds)
+{
+    MergeScratch &ms = dst->merge;
+    const int32_t capacity = records + 1;
+    const unsigned scanGrid = (unsigned)std::min(grid_for((size_t)records, 256), 4096);
+    int rc;
+    for (;;) {
+        if ((rc = vh_reset_mutexes(dst)) != VH_OK) return rc;
+        rc = launch(dst, kPhaseClaim, claim_bins_kernel, dim3(bin_parts(capacity), 1), dim3(256), dst->fp, dst->dp,
+                    (const int4 *)bin, capacity, capacity);
+        if (rc == VH_OK) rc = launch(dst, kPhaseCommit, alloc_commit_kernel, dim3(32), dim3(256), dst->fp, dst->dp);
+        if (rc != VH_OK) return rc;
+        VH_HIP(hipMemsetAsync(ms.words.get() + kMergeMissing, 0, sizeof(unsigned long long), dst->stream));
+        rc = launch(dst, kPhaseCommit, merge_missing_kernel, dim3(scanGrid), dim3(256), dst->fp, dst->dp, (const int4 *)bin, records,
+                    ms.words.get());
+        const int32_t allocatedLast = *rounds ? *allocatedNow : allocatedBefore;
+        if (rc == VH_OK) rc = merge_read(dst, words, allocatedNow);
+        if (rc != VH_OK) return rc;
+        *rounds += 1;
+        if (words[kMergeMissing] == 0 || *allocatedNow == allocatedLast) break;
+    }
+    return VH_OK;
+}
+
 // colorWeightMax == 0: vh_merge.  1..255: vh_merge_color -- the same call with the colour step in its update launch, where src
 // has colour to give.
 static int merge_impl(vh_context *dst, vh_context *src, const float src_to_dst[16], int32_t mode, int32_t colorWeightMax,
@@ -80,29 +108,14 @@ static int merge_impl(vh_context *dst, vh_context *src, const float src_to_dst[1
                 (uint32_t)src->numEntries, T, vsSrc, vsDst, ms.words.get(), bin, capacity);
     if (rc != VH_OK) return rc;
 
-    // 2. allocation: the bin goes through the claim + commit path, one lock epoch per round, until nothing is missing or a round
-    // allocates nothing (buckets full, heap empty).  Every round that goes on has allocated a block, so the heap bounds the loop.
-    const unsigned scanGrid = (unsigned)std::min(grid_for((size_t)records, 256), 4096);
-    for (;;) {
-        if ((rc = vh_reset_mutexes(dst)) != VH_OK) return rc;
-        rc = launch(dst, kPhaseClaim, claim_bins_kernel, dim3(bin_parts(capacity), 1), dim3(256), dst->fp, dst->dp,
-                    (const int4 *)bin, capacity, capacity);
-        if (rc == VH_OK) rc = launch(dst, kPhaseCommit, alloc_commit_kernel, dim3(32), dim3(256), dst->fp, dst->dp);
-        if (rc != VH_OK) return rc;
-        VH_HIP(hipMemsetAsync(ms.words.get() + kMergeMissing, 0, sizeof(unsigned long long), dst->stream));
-        rc = launch(dst, kPhaseCommit, merge_missing_kernel, dim3(scanGrid), dim3(256), dst->fp, dst->dp, (const int4 *)bin, records,
-                    ms.words.get());
-        const int32_t allocatedLast = st.rounds ? allocatedNow : allocatedBefore;
-        if (rc == VH_OK) rc = merge_read(dst, words, &allocatedNow);
-        if (rc != VH_OK) return rc;
-        st.rounds += 1;
-        if (words[kMergeMissing] == 0 || allocatedNow == allocatedLast) break;
-    }
+    // 2. allocation
+    if ((rc = bin_alloc_rounds(dst, bin, records, allocatedBefore, words, &allocatedNow, &st.rounds)) != VH_OK) return rc;
     st.allocated = (uint32_t)(allocatedNow - allocatedBefore);
     st.unplaced = words[kMergeMissing];
 
     // 3. update: the distinct candidate blocks dst holds become its compact list (alloc_commit_kernel has zeroed the count), and
     // one launch in the TSDF update's shape runs over it
+    const unsigned scanGrid = (unsigned)std::min(grid_for((size_t)records, 256), 4096);
     rc = launch(dst, kPhaseFlatten, merge_list_kernel, dim3(scanGrid), dim3(256), dst->fp, dst->dp, (const int4 *)bin, records);
     if (rc != VH_OK) return rc;
     dst->compactArmed = false;

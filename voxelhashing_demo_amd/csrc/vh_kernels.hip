@@ -33,6 +33,9 @@
 //   vh_color.hip       the model in colour: a second volume of one word per voxel, the registered colour image fused into the
 //                      voxels near the surface in the TSDF update's launch shape and taken back out of them, colour at world
 //                      points with the sampler's shared look-ups (no counterpart in the reference)
+//   vh_stream.hip      block streaming: the blocks of a region out of the model as records (ordered list, pack, the deletion
+//                      path) and records back in (classification, the bin insertion path, one placed record per key); no
+//                      counterpart in the reference
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -60,3 +63,4 @@
 #include "vh_track.hip"
 #include "vh_merge.hip"
 #include "vh_color.hip"
+#include "vh_stream.hip"

@@ -14,6 +14,7 @@ from . import _lib as L
 
 ENTRY_DTYPE = np.dtype([("pos", "<i4", (3,)), ("ptr", "<i4"), ("offset", "<i4")])
 VOXEL_DTYPE = np.dtype([("sdf", "<f4"), ("weight", "<f4")])
+RECORD_DTYPE = np.dtype([("pos", "<i4", (3,)), ("reserved", "<i4"), ("voxels", VOXEL_DTYPE, (512,))])    # vh_view_record, 4112 bytes
 
 
 def default_params(**overrides) -> L.HashTableParams:
@@ -405,6 +406,79 @@ class SDFHashtable:
 
     def garbage_collect(self, sdf_threshold: float):
         L.check(self._lib.vh_garbage_collect(self._h, float(sdf_threshold)), "vh_garbage_collect")
+
+    # ---- block streaming ----
+    @staticmethod
+    def _stream_region(region):
+        """region: streaming.box(...) / streaming.sphere(...) -- a dict {kind, invert, lo, hi, centre, radius}."""
+        r = L.StreamRegion()
+        r.kind, r.invert = int(region["kind"]), int(bool(region.get("invert", False)))
+        r.block_lo[:] = [int(v) for v in region.get("lo", (0, 0, 0))]
+        r.block_hi[:] = [int(v) for v in region.get("hi", (0, 0, 0))]
+        r.centre[:] = [float(v) for v in region.get("centre", (0.0, 0.0, 0.0))]
+        r.radius = float(region.get("radius", 0.0))
+        return r
+
+    def stream_out_into(self, region, capacity: int, records, colors=None):
+        """vh_stream_out into caller-owned device buffers: records uint8 [capacity, 4112] (vh_view_record), colors uint32
+        [capacity, 512] or None -- then THE COLOUR OF THE REMOVED BLOCKS IS DROPPED.  Returns (selected, written): the allocated
+        blocks the region holds and the first `written` = min(selected, capacity) of them in entry order, which have left the
+        model.  capacity 0 with None buffers only counts.  Synchronises."""
+        sel, wr = C.c_uint64(), C.c_uint64()
+        r = self._stream_region(region)
+        L.check(self._lib.vh_stream_out(self._h, C.byref(r), int(capacity), _dev_ptr(records), _dev_ptr(colors), C.byref(sel),
+                                        C.byref(wr)), "vh_stream_out")
+        return int(sel.value), int(wr.value)
+
+    def stream_in_from(self, records, n: int = None, colors=None, status=None) -> dict:
+        """vh_stream_in from device buffers: records uint8 [n, 4112], colors uint32 [n, 512] or None, status int32 [n] or None
+        (receives STREAM_PLACED / PRESENT / UNPLACED / FOREIGN per record).  Returns vh_stream_stats as a dict.  Synchronises."""
+        n = int(records.shape[0]) if n is None else int(n)
+        st = L.StreamStats()
+        L.check(self._lib.vh_stream_in(self._h, n, _dev_ptr(records), _dev_ptr(colors), _dev_ptr(status), C.byref(st)), "vh_stream_in")
+        return st.as_dict()
+
+    def stream_count(self, region) -> int:
+        """The allocated blocks `region` holds; nothing changes."""
+        return self.stream_out_into(region, 0, None, None)[0]
+
+    def stream_out(self, region, capacity: int = None, colors: bool = None) -> dict:
+        """Takes the blocks of `region` out of the model and returns them in host memory: {"keys": int32 [n, 3], "voxels":
+        [n, 512] {sdf, weight}, "colors": uint32 [n, 512] or None, "selected": the blocks the region held}.  n = min(selected,
+        capacity); capacity=None counts first and takes them all.  colors=None: the colour travels if the table has any;
+        colors=False drops it."""
+        colors = self.has_color() if colors is None else bool(colors)
+        cap = self.stream_count(region) if capacity is None else min(int(capacity), int(self.params.numVoxelBlocks))
+        recs = np.zeros(cap, RECORD_DTYPE)
+        cols = np.zeros((cap, 512), np.uint32) if colors else None
+        sel, wr = C.c_uint64(), C.c_uint64()
+        r = self._stream_region(region)
+        L.check(self._lib.vh_stream_out_host(self._h, C.byref(r), cap, recs.ctypes.data_as(C.c_void_p) if cap else None,
+                                             cols.ctypes.data_as(C.c_void_p) if colors and cap else None, C.byref(sel), C.byref(wr)),
+                "vh_stream_out_host")
+        n = int(wr.value)
+        return {"keys": recs["pos"][:n].copy(), "voxels": recs["voxels"][:n].copy(), "colors": cols[:n].copy() if colors else None,
+                "selected": int(sel.value)}
+
+    def stream_in(self, chunk) -> dict:
+        """Puts the blocks of `chunk` (what stream_out returns; "colors" may be None or missing) back into the model.  Returns
+        vh_stream_stats as a dict plus "status": int32 [n], STREAM_PLACED / PRESENT / UNPLACED / FOREIGN per record."""
+        keys = np.asarray(chunk["keys"], np.int32).reshape(-1, 3)
+        n = len(keys)
+        recs = np.zeros(n, RECORD_DTYPE)
+        recs["pos"] = keys
+        recs["voxels"] = np.asarray(chunk["voxels"], VOXEL_DTYPE).reshape(n, 512)
+        cols = chunk.get("colors")
+        if cols is not None:
+            cols = np.ascontiguousarray(np.asarray(cols, np.uint32).reshape(n, 512))
+        status = np.zeros(n, np.int32)
+        st = L.StreamStats()
+        L.check(self._lib.vh_stream_in_host(self._h, n, recs.ctypes.data_as(C.c_void_p) if n else None,
+                                            cols.ctypes.data_as(C.c_void_p) if cols is not None and n else None,
+                                            status.ctypes.data_as(C.c_void_p) if n else None, C.byref(st)), "vh_stream_in_host")
+        out = st.as_dict()
+        out["status"] = status
+        return out
 
     # ---- the model as geometry (DESIGN.md "mesh") ----
     @staticmethod
