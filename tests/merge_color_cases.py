@@ -3,7 +3,8 @@ frames, pools and transforms of tests/merge_cases.py with a colour image per fra
 colour schedule of the two models, and the cases (transform, voxel-size ratio, mode, weight_max) the GPU tests merge.
 
 src is fused from frames 0 and 1 and coloured twice per frame (two different images), so that its counts reach 4 and a
-weight_max of 3 binds; dst is fused from frame 2 and coloured once.  Colour lives within 1.5 voxels of the surface, so two
+weight_max of 3 binds (the rest of the range, counts up to 255 on either side, is tests/color_count_cases.py's: crafted words); dst
+is fused from frame 2 and coloured once.  Colour lives within 1.5 voxels of the surface, so two
 coloured voxels meet only where the moved src surface lies on dst's: under merge_cases.OBLIQUE (27 degrees) the rule finds no
 such voxel under REFERENCE semantics, under CLOSE -- the same axis, 3 degrees, a translation off the lattice -- some hundreds in
 both (tests/test_merge_color_ref_cpu.py checks every branch for every case)."""
