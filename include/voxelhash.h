@@ -374,13 +374,16 @@ int vh_debug_icp_layout(const struct vh_icp *icp, int32_t out[3]);
  *     "pipeline_shards"  0 | 1 | 2: the same for a shard's multi-camera frames (vh_apply_frames_batch)
  *     "fused_frame"      1 (default): vh_integrate as two launches; 0: the four step kernels of the step-level entry points
  *     "walk_nt"          non-temporal loads in the reference walk (default: on when the table exceeds the 256 MiB Infinity Cache)
+ *     "walk_reverse"     1 (default): the reference walk sweeps the table forward in one launch and backward in the next, each tile on
+ *                        the same XCD, so that the tail of a sweep is still in that XCD's L2; 0: always forward (same compact SET)
  *     "integrate_grid", "commit_blocks"   workgroups of the TSDF update / of the commit phase in the two-launch frame
  *     "gen_frames_per_launch"  1..8 (default 4): frames of a batch one key-generation launch of vh_generate_keys*_batch takes
  *     "spin_limit"       polls a workgroup of a serialised one-launch frame waits for the pending commit phase (0: default)
  *   the raycast:
  *     "raycast_mode" (VH_RAYCAST_DDA | VH_RAYCAST_FIXED_STEP), "raycast_beam" (0 | 1 | 2 | 3 = by the view, default)
  *   formats / test hooks:
- *     "packet_format" (VH_PACKET_F32 / VH_PACKET_U16, below), "cand_capacity" (a smaller candidate list: vh_counters.cand_overflow)
+ *     "packet_format" (VH_PACKET_F32 / VH_PACKET_U16, below), "cand_capacity" (a smaller candidate list: vh_counters.cand_overflow),
+ *     "walk_short" (1, what every table gets: walk tiles of 1024 entries; 0: of 2048, the generic build -- tests/test_gpu_walk_order.py)
  * Variants that were measured and lost (the persistent walk, 8 entries per lane in the frame's walk, the generic build where a
  * lean one exists, the raycast as three launches, 16x4 ray patches, LDS staging of the TSDF update and of the raycast's
  * blocks ...) are not in the library: DESIGN_LOG.md names the commit that last held each. */

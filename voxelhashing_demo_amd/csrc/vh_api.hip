@@ -201,6 +201,8 @@ struct vh_context {
     // 4 = the walk over the bucket-occupancy bitmap and the non-empty buckets (same compact set, 2-11 x the frames/s): the default
     // since round 6.  The reference's walk stays selectable, and it is what bench.py's `value` measures (20*N).
     int flattenVariant = 4;
+    int walkReverse = 1;           // option "walk_reverse": the reference's walk alternates its direction from launch to launch (vh_walk.hip: walk_tile)
+    uint32_t walkBackward = 0;     // ... and the direction of the next launch that carries it
     uint32_t candAllocated = 0;    // records the candidate buffer holds (dp.candCapacity <= this)
     uint32_t allocEpoch = 0;       // lock epoch (epochTotal) of the last allocBlocks (overflow list: one per epoch)
     uint32_t epochTotal = 0;       // lock epochs since creation (fp.epoch is the 9-bit epoch of the claim words)
@@ -438,7 +440,9 @@ static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_contex
     // A table beyond the 256 MiB Infinity Cache is walked with non-temporal loads: a pure read of 419 MB runs
     // at 7.0 instead of 6.0 TB/s that way (tools/micro/membw.hip) and the voxel blocks stay cached across
     // frames (C3: launch 1 76.2 -> 70.2 us, launch 2 13.5 -> 11.7 us); a resident table (C2, 105 MB) loses
-    // 2 % with them.  Option "walk_nt" overrides.
+    // 2 % with them.  Option "walk_nt" overrides.  The rule holds with the alternating sweep (option "walk_reverse", on at
+    // every size) as well: C3's pipelined launch, same process, 67.9 us non-temporal and alternating, 68.9 non-temporal and
+    // forward, 72.3 plain and alternating (the Infinity Cache then keeps a tail of the table), 83.9 plain and forward.
     if (c->numEntries * sizeof(VoxelEntry) > ((size_t)256 << 20)) fp.flags |= kFlagWalkNt;
     fp.flags |= kFlagWalkShort;          // 4 entries per lane in the frame's walk
     const size_t npix = (size_t)cfg->width * cfg->height;

@@ -89,6 +89,17 @@ static uint32_t walk_blocks(const vh_context *c)
     return (uint32_t)grid_for(c->numEntries, kFlattenThreads * ((c->fp.flags & kFlagWalkShort) ? kEntriesPerLaneShort : kEntriesPerLane));
 }
 
+// The reference's walk in the single-camera launches: its ordinals run over groups of 8 workgroups (the tiles rounded up to a
+// multiple of 8; vh_walk.hip: walk_tile), and its direction alternates from one launch that carries it to the next, in every
+// context (option "walk_reverse" 1, the default; 0: always forward).
+static inline uint32_t groups_of_8(uint32_t n) { return (n + 7u) / 8u; }
+static uint32_t take_walk_direction(vh_context *c)
+{
+    const uint32_t reverse = c->walkReverse ? c->walkBackward : 0u;
+    c->walkBackward ^= 1u;
+    return reverse;
+}
+
 // ... of the multi-camera walk: the reference's walk with 4 entries per lane from 32 MB of entries on, else 8; the index walk
 // for flatten_variant 4 without the overflow list (holes and chains take the reference's walk)
 static bool multi_walk_indexed(const vh_context *c) { return c->flattenVariant == kWalkIndexed && !(c->fp.flags & kFlagOverflow); }
@@ -108,12 +119,11 @@ static int with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::fals
 
 static int launch_flatten(vh_context *c)
 {
-    const dim3 grid(walk_blocks(c));
     if (c->flattenVariant == kWalkIndexed)
-        return launch(c, kPhaseFlatten, flatten_kernel<kWalkIndexed>, grid, dim3(kFlattenThreads), c->fp, c->dp,
-                      (uint32_t)c->numEntries);
-    return launch(c, kPhaseFlatten, flatten_kernel<kWalkStridedBallot>, grid, dim3(kFlattenThreads), c->fp, c->dp,
-                  (uint32_t)c->numEntries);
+        return launch(c, kPhaseFlatten, flatten_kernel<kWalkIndexed>, dim3(walk_blocks(c)), dim3(kFlattenThreads), c->fp, c->dp,
+                      (uint32_t)c->numEntries, 0u);
+    return launch(c, kPhaseFlatten, flatten_kernel<kWalkStridedBallot>, dim3(8u * groups_of_8(walk_blocks(c))), dim3(kFlattenThreads),
+                  c->fp, c->dp, (uint32_t)c->numEntries, take_walk_direction(c));
 }
 
 template <class Depth>
@@ -388,8 +398,25 @@ static int launch_pipelined(vh_context *c, const In *in, int newSensor, const fl
     // C3 26.1 -> 25.1 us, while C2 prefers the 512 it has, 8.7 against 9.0)
     if (hasOld && a.walkIndexed && large) a.integrateBlocks *= 2u;
     a.numEntries = (uint32_t)c->numEntries;
-    a.claimSpan = claim_span(c, a.claimBlocks, a.walkBlocks);
-    a.claimRatio = claim_ratio(a.claimBlocks, a.claimSpan);
+    a.walkGroups = 0u; a.walkReverse = 0u;
+    uint32_t claimWalk = a.claimBlocks + a.walkBlocks;          // workgroups of the two roles
+    if (a.walkIndexed) {
+        a.claimSpan = claim_span(c, a.claimBlocks, a.walkBlocks);
+        a.claimRatio = claim_ratio(a.claimBlocks, a.claimSpan);
+    } else {
+        // The reference's walk: every role count a multiple of 8, so that the walk workgroup of ordinal w has blockIdx = w
+        // (mod 8) in every launch (vh_frame.hip: grouped_role); span and ratio count groups.  The surplus commit and
+        // integrate workgroups stride over the candidates and the list like the others; the surplus claim and walk
+        // workgroups return.  The direction changes hands with every launch that carries a walk, not with a flush launch.
+        a.commitBlocks = 8u * groups_of_8(a.commitBlocks);
+        a.integrateBlocks = 8u * groups_of_8(a.integrateBlocks);
+        const uint32_t claimGroups = groups_of_8(a.claimBlocks);
+        a.walkGroups = groups_of_8(a.walkBlocks);
+        a.claimSpan = claim_span(c, claimGroups, a.walkGroups);
+        a.claimRatio = claim_ratio(claimGroups, a.claimSpan);
+        if (hasNew) a.walkReverse = take_walk_direction(c);
+        claimWalk = 8u * (claimGroups + a.walkGroups);
+    }
     a.planeNew = (hasNew && !newSensor) ? c->planeBuf[r.newParity].get() : nullptr;
     a.rawNew = (hasNew && newSensor) ? c->rawBuf[r.newParity].get() : nullptr;
     a.filter = c->claimFilter;
@@ -398,7 +425,7 @@ static int launch_pipelined(vh_context *c, const In *in, int newSensor, const fl
 #ifdef VH_DEBUG_SKIP_ROLES
     a.skipRoles = (uint32_t)c->debugSkipRoles;
 #endif
-    const dim3 grid(a.commitBlocks + a.integrateBlocks + a.claimBlocks + a.walkBlocks);
+    const dim3 grid(a.commitBlocks + a.integrateBlocks + claimWalk);
     In inNew{};
     if (hasNew) inNew = *in;
     if (hasOld && c->pend.sensor) {
@@ -471,9 +498,17 @@ extern "C" int vh_flush(vh_context *c)
 template <int kKind, class In>
 static int launch_scan_claim(vh_context *c, const In &in, uint32_t claimBlocks, uint32_t scanBlocks, float *planeOut)
 {
+    if (kKind != kWalkIndexed) {
+        // the reference's walk: both roles in groups of 8 workgroups (vh_frame.hip: grouped_role), span and ratio in groups
+        const uint32_t claimGroups = groups_of_8(claimBlocks), walkGroups = groups_of_8(scanBlocks);
+        const uint32_t span = claim_span(c, claimGroups, walkGroups);
+        return launch(c, kPhaseFrameScanClaim, frame_scan_claim_kernel<kKind, In>, dim3(8u * (claimGroups + walkGroups)),
+                      dim3(256), c->fp, c->dp, in, (uint32_t)c->numEntries, claimBlocks, c->fusedParity, planeOut,
+                      span, claim_ratio(claimGroups, span), walkGroups, take_walk_direction(c));
+    }
     return launch(c, kPhaseFrameScanClaim, frame_scan_claim_kernel<kKind, In>, dim3(claimBlocks + scanBlocks),
                   dim3(256), c->fp, c->dp, in, (uint32_t)c->numEntries, claimBlocks, c->fusedParity, planeOut,
-                  claim_span(c, claimBlocks, scanBlocks), claim_ratio(claimBlocks, claim_span(c, claimBlocks, scanBlocks)));
+                  claim_span(c, claimBlocks, scanBlocks), claim_ratio(claimBlocks, claim_span(c, claimBlocks, scanBlocks)), 0u, 0u);
 }
 
 // the packed camera-z plane launch 1 leaves for launch 2 (vertex-map input only)

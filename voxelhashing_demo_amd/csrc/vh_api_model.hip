@@ -416,6 +416,11 @@ extern "C" int vh_set_option(vh_context *c, const char *name, int value)
         c->fp.flags = value ? (c->fp.flags | kFlagWalkNt) : (c->fp.flags & ~kFlagWalkNt);
         return VH_OK;
     }
+    if (std::strcmp(name, "walk_reverse") == 0) { c->walkReverse = value != 0; return VH_OK; }     // (0: every walk forward)
+    if (std::strcmp(name, "walk_short") == 0) {       // test hook: 4 (the default of every table) or 8 entries per lane in the frame's walk
+        c->fp.flags = value ? (c->fp.flags | kFlagWalkShort) : (c->fp.flags & ~kFlagWalkShort);
+        return VH_OK;
+    }
 #ifdef VH_DEBUG_SKIP_ROLES      // diagnostics builds only (make EXTRA=-DVH_DEBUG_SKIP_ROLES): the check costs the product launch a scalar load per workgroup
     if (std::strcmp(name, "debug_skip_roles") == 0 && value >= 0 && value < 32) {
         c->debugSkipRoles = value;

@@ -19,12 +19,53 @@ namespace vh {
 // planeOut (nullable): the claim half also leaves the camera z of every pixel in a packed float plane
 // for launch 2 to gather from -- 4 bytes per pixel written once here instead of a 16-byte-strided
 // gather from the vertex map there (C3, launch 2: 72 MB of traffic for 40 MB of algorithmic bytes).
+//
+// Under the reference's walk the two roles are dealt in GROUPS of 8 consecutive workgroups (grouped_role): r = the
+// workgroup's index among the claim + walk workgroups, g = r >> 3 its group, q = r & 7 its class.  Every class takes as
+// many claim tiles as there are claim groups, where ITS multiply-high steps -- the classes q / 8 of a step apart, so the
+// claim tiles stay spread over the span one by one (whole groups claiming together: 53.9 k frames/s on C2 against 54.1 k)
+// -- and a walk workgroup's ordinal w = r - 8 * (claims of its class before it) keeps w = r (mod 8).  With every role
+// count ahead of them a multiple of 8 too (the host's to ensure), the tile of ordinal w (vh_walk.hip: walk_tile) is read
+// by a workgroup of the same blockIdx % 8 in every launch.  Claim indices 8 * step + q beyond claimBlocks fill up the
+// last claim group: those workgroups return.  claimSpan and claimRatio count groups here; at g = claimSpan every class
+// has had ceil(claimBlocks / 8) claims (claimRatio * claimSpan exceeds that many steps by less than claimSpan / 2^32).
+// Returns true for a claim workgroup (index: its claim tile, to be tested against claimBlocks), false for a walk
+// workgroup (index: its ordinal).
+__device__ __forceinline__ bool grouped_role(uint32_t r, uint32_t claimBlocks, uint32_t claimSpan, uint32_t claimRatio,
+                                             uint32_t &index)
+{
+    const uint32_t g = r >> 3, q = r & 7u;
+    uint32_t before = (claimBlocks + 7u) >> 3;
+    if (g < claimSpan) {
+        const unsigned long long phase = (unsigned long long)q << 29;          // q / 8 of a step
+        before = (uint32_t)(((unsigned long long)g * claimRatio + phase) >> 32);
+        const uint32_t after = (uint32_t)(((unsigned long long)(g + 1u) * claimRatio + phase) >> 32);
+        if (after != before) { index = 8u * before + q; return true; }
+    }
+    index = r - 8u * before;
+    return false;
+}
+
+// walkGroups, walkReverse: of the reference's walk (walk_tile); the walk-free frame (kKind = kWalkIndexed) keeps the
+// single dealing described below and ignores them
 template <int kKind, class In>
 __global__ __launch_bounds__(256) void frame_scan_claim_kernel(const FrameParams fp, const DevPtrs dp, const In in,
                                                                uint32_t numEntries, uint32_t claimBlocks,
                                                                int parity, float *__restrict__ planeOut, uint32_t claimSpan,
-                                                               uint32_t claimRatio)
+                                                               uint32_t claimRatio, uint32_t walkGroups, uint32_t walkReverse)
 {
+    if constexpr (kKind != kWalkIndexed) {
+        uint32_t index;
+        if (grouped_role(blockIdx.x, claimBlocks, claimSpan, claimRatio, index)) {
+            if (index >= claimBlocks) return;
+            __builtin_amdgcn_s_setprio(3);
+            claim_tile(fp, dp, in, index, kFusedCand + parity, kNoPending, planeOut);
+        } else {
+            flatten_tile<kKind>(fp, dp, numEntries, walk_tile(index, walkGroups, walkReverse),
+                                CompactOut{kScanCount + parity, kScanCountB + parity, numEntries}, 8u * walkGroups);
+        }
+        return;
+    }
     // The two roles are interleaved over the grid in proportion (block b is a claim block when
     // floor((b+1)*claim/total) steps): workgroups are dispatched roughly in index order, and
     // with all claim blocks in front a large image would fill the chip with latency-bound
@@ -171,7 +212,8 @@ struct PipeArgs {
     uint32_t hasNew, hasOld;               // first launch of a run: no old frame; flush launch: no new frame
     uint32_t walkIndexed;                  // flatten_variant 4: the walk role runs over the bucket-occupancy bitmap
     uint32_t claimPerWave;                 // the claim role takes a launch tile per WAVE (claim_tile_wave; the walk-free builds only)
-    uint32_t claimSpan, claimRatio;        // claim tiles are interleaved with the first claimSpan - claimBlocks walk tiles
+    uint32_t claimSpan, claimRatio;        // claim tiles are interleaved with the first walk tiles: over claimSpan groups of 8 workgroups (grouped_role)
+    uint32_t walkGroups, walkReverse;     // the reference's walk: its ordinals run over 8 * walkGroups >= walkBlocks, backward if walkReverse (vh_walk.hip: walk_tile)
     float *planeNew;                       // private depth copies written by claim(new) ...
     uint16_t *rawNew;
     uint32_t *filter;                      // claim filters (vh_alloc.hip: pend_maybe), three of kPendFilterWords words
@@ -256,15 +298,12 @@ __device__ __forceinline__ void frame_pipelined(const FrameParams &fpNew, const 
     }
     else if (b < a.commitBlocks + a.integrateBlocks) { role = 1; index = b - a.commitBlocks; }
     else {
-        // the claim tiles are spread over the first a.claimSpan of the claim + walk workgroups (multiply-high
-        // by a.claimRatio = ceil(claimBlocks * 2^32 / claimSpan): no division in the kernel)
-        const uint32_t r = b - a.commitBlocks - a.integrateBlocks;
-        if (r < a.claimSpan) {
-            const uint32_t before = __umulhi(r, a.claimRatio), after = __umulhi(r + 1u, a.claimRatio);
-            if (after != before) { role = 2; index = before; } else { role = 3; index = r - before; }
-        } else {
-            role = 3; index = r - a.claimBlocks;
-        }
+        // the claim tiles are spread, in groups of 8, over the first a.claimSpan groups of the claim + walk workgroups
+        // (grouped_role: multiply-high by a.claimRatio = ceil(claimGroups * 2^32 / claimSpan), no division in the kernel;
+        // the host keeps a.commitBlocks + a.integrateBlocks a multiple of 8, so a walk ordinal = blockIdx mod 8)
+        const bool claims = grouped_role(b - a.commitBlocks - a.integrateBlocks, a.claimBlocks, a.claimSpan, a.claimRatio, index);
+        role = claims ? 2u : 3u;
+        if (claims && index >= a.claimBlocks) return;          // (fills up the last claim group)
     }
 #ifdef VH_DEBUG_SKIP_ROLES
     if (a.skipRoles & (1u << role)) return;
@@ -309,7 +348,7 @@ __device__ __forceinline__ void frame_pipelined(const FrameParams &fpNew, const 
             flatten_index_tile(fpNew, dpNew, index, CompactOut{kPipeScan + a.setNew, kPipeScanB + a.setNew, a.numEntries},
                                pend);                                              // (opt-in: not the reference's walk)
         } else {
-            flatten_tile_ballot(fpNew, dpNew, a.numEntries, index,
+            flatten_tile_ballot(fpNew, dpNew, a.numEntries, walk_tile(index, a.walkGroups, a.walkReverse),
                                 CompactOut{kPipeScan + a.setNew, kPipeScanB + a.setNew, a.numEntries}, pend);
         }
         return;

@@ -25,6 +25,13 @@ namespace vh {
 // 69.5 us with non-temporal loads in both, C2 17.7 vs 17.1 us; one chunk per wave and twice the workgroups:
 // C2 18.3 vs 17.0 us fused, 16.1 vs 15.8 us as a launch of its own -- at 15.8 us = 6.6 TB/s the plain walk
 // already reads the 105 MB table as fast as the best form of the ceiling probe).
+// That ceiling is the rate of the fabric behind the eight L2s, not of the L2s: swept in one direction frame after frame,
+// an XCD's eighth of the table (13 MB on C2) passes cyclically through its 4 MiB L2 and hits nothing.  So the sweep
+// alternates its direction from launch to launch and every tile stays on its XCD (walk_tile below, option
+// "walk_reverse"): what an XCD read last is what it reads first in the next frame.  Same box, same process, C2: the
+// pipelined launch 18.97 -> 17.43 us, launch 1 of the two-launch frame 16.31 -> 14.03 us; C3 (419 MB, beyond the
+// Infinity Cache too) 68.9 -> 67.9 us with non-temporal loads and 83.9 -> 72.3 us without, so the non-temporal rule
+// of such tables stays (DESIGN_LOG.md, "The table walk, forward and backward").
 constexpr int kFlattenThreads = 256;
 #ifndef VH_ENTRIES_PER_LANE
 #define VH_ENTRIES_PER_LANE 8
@@ -75,6 +82,22 @@ __device__ __forceinline__ void compact_append(const DevPtrs &dp, const CompactO
         const uint32_t pos = (uint32_t)base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
         dp.compact[toB ? out.numEntries - 1u - pos : pos] = ent;
     }
+}
+
+// Which tile the walk workgroup of ordinal w takes (the reference's walk: the fused launches, the pipelined launch and the
+// stand-alone flatten_kernel).  The ordinals run over Wp = 8 * groups, the number of tiles rounded up to a multiple of 8
+// (a surplus tile finds e >= numEntries in walk_load_tile and falls out), and the launches place ordinal w in a workgroup
+// with blockIdx = w (mod 8): like xcd_contiguous (vh_device.h) this relies on workgroups going to the 8 XCDs round robin,
+// for speed only.  The class q = w & 7 of a tile is kept, so a tile is read through the same XCD's L2 in every launch;
+// within the class the step s = w >> 3 runs forward or, with `reverse` (option "walk_reverse", toggled by the host after
+// every launch that carried the walk), backward -- the megabytes an XCD read last in one frame are the ones it reads
+// first in the next, while they are still in its 4 MiB L2.  Swept in the same direction every frame, a 13 MB eighth of
+// C2's table goes through that L2 cyclically and hits nothing.  A bijection of [0, Wp) for either direction, whatever
+// the placement; reverse = 0 is tile = w.
+__device__ __forceinline__ uint32_t walk_tile(uint32_t w, uint32_t groups, uint32_t reverse)
+{
+    const uint32_t q = w & 7u, s = w >> 3;
+    return (reverse ? groups - 1u - s : s) * 8u + q;
 }
 
 // strided walk with one ballot + atomic per unrolled entry slot (hits are rare on small scenes)
@@ -397,11 +420,13 @@ __device__ __forceinline__ void flatten_tile(const FrameParams &fp, const DevPtr
         flatten_tile_ballot(fp, dp, numEntries, tileIndex, out);
 }
 
+// (the reference's walk: a grid of 8 * groups workgroups, the tiles rounded up -- walk_tile; the index walk: one per tile)
 template <int kKind>
 __global__ __launch_bounds__(kFlattenThreads) void flatten_kernel(const FrameParams fp, const DevPtrs dp,
-                                                                  uint32_t numEntries)
+                                                                  uint32_t numEntries, uint32_t reverse)
 {
-    flatten_tile<kKind>(fp, dp, numEntries, blockIdx.x, CompactOut{kCompactCount, -1, numEntries}, gridDim.x);
+    const uint32_t tile = kKind == kWalkIndexed ? blockIdx.x : walk_tile(blockIdx.x, gridDim.x >> 3, reverse);
+    flatten_tile<kKind>(fp, dp, numEntries, tile, CompactOut{kCompactCount, -1, numEntries}, gridDim.x);
 }
 
 }  // namespace vh
