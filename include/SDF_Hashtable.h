@@ -97,6 +97,12 @@ public:
      * weight (optional) one per point, gradient (optional) three per point, per world metre.  Synchronises. */
     void sampleSdf(const std::vector<float> &points, int mode, std::vector<float> &sdf, std::vector<float> *weight = nullptr,
                    std::vector<float> *gradient = nullptr);
+    /* The Euclidean signed distance to the surface on the lattice (vh_esdf_lattice, through host buffers): for the voxels
+     * lo <= g < lo + dims (x fastest) the exact signed squared distance, in voxels, to the nearest voxel of the other class up
+     * to `radius` voxels (1 .. VH_ESDF_MAX_RADIUS) in dist2 (VH_ESDF_FAR, VH_ESDF_NONE), and / or the same in metres in distance
+     * (+-inf, NaN); unknown = VH_ESDF_UNKNOWN_KEEP, _FREE or _OCCUPIED.  At least one of the two outputs.  Synchronises. */
+    void esdfLattice(const int32_t lo[3], const int32_t dims[3], int radius, int unknown, std::vector<int32_t> *dist2,
+                     std::vector<float> *distance);
     /* Where rays meet the surface (vh_cast_rays, through host buffers): rays = 8 floats per ray (origin, t_min, direction, t_max,
      * the layout of vh_ray); depthPlane = four floats (one plane places the samples of all rays: row 2 of a pose's inverse gives
      * the raycast's depths) or nullptr (along each ray); t = one float per ray, NaN where there is no hit; normals (optional)

@@ -673,6 +673,51 @@ int vh_sample_lattice(vh_context *ctx, const int32_t lo[3], const int32_t dims[3
                       float *d_sdf        /* dims[0]*dims[1]*dims[2] floats, x fastest */,
                       float *d_weight     /* the same size or NULL */);
 
+/* The Euclidean signed distance field (ESDF) on the lattice: for every voxel of a box the exact squared distance, in voxels,
+ * to the nearest voxel of the other class, up to a radius (tests/esdf_ref.py is the rule in executable
+ * form).  Integers throughout: the same model gives the same bits.
+ *   Classes.  A voxel g is valid by the rule above (block allocated in this table / shard, weight > 0, sdf not NaN).  A
+ *     valid voxel is INSIDE iff sdf < 0 (-inf is inside, -0.0 and +0.0 are not), every other valid voxel is OUTSIDE, every
+ *     other voxel of the infinite lattice is UNKNOWN.  `unknown` remaps the unknown voxels before anything else happens:
+ *     VH_ESDF_UNKNOWN_KEEP leaves them unknown, _FREE makes them outside and _OCCUPIED inside, in every respect.
+ *   Distance.  With R = radius (1 .. VH_ESDF_MAX_RADIUS) and d2(g, s) = |g - s|^2: P(g) = the minimum of d2(g, s) over the
+ *     inside voxels s with d2 <= R^2, N(g) the same over the outside voxels; either may be "none".  The result D(g) is
+ *       for an outside voxel  P(g), or VH_ESDF_FAR where there is none;
+ *       for an inside voxel  -N(g), or -VH_ESDF_FAR where there is none;
+ *       for an unknown voxel (under KEEP only)  VH_ESDF_NONE.
+ *     The sites are voxel centres: across a surface the values go ..., 4, 1, -1, -4, ... and never 0.
+ *   The sites are those of the whole model, not of the box: D(g) depends on the voxels within R of g only, so two calls
+ *     agree wherever their boxes overlap.
+ *   d_distance, in metres: sign(D) * (sqrtf((float)|D|) * voxelSize), each operation rounded to fp32 on its own and the
+ *     square root correctly rounded; +-inf for +-VH_ESDF_FAR, NaN for VH_ESDF_NONE.
+ * The layout of both outputs is vh_sample_lattice's.  The call only enqueues work on the context's stream, behind every
+ * frame queued so far (a pending pipelined frame is launched first); it reads nothing back, does not synchronise, allocates
+ * nothing (the caller brings the workspace, of at least vh_esdf_workspace_bytes(dims, radius) bytes, 16-byte aligned; nothing
+ * beyond that size is written) and changes nothing in the model.  It works on shards (a block of another shard is unknown)
+ * and on view tables, with or without the overflow list.  A zero entry of dims: VH_OK, nothing is launched, no workspace
+ * is needed (vh_esdf_workspace_bytes reports 0).  VH_ERR_INVALID_ARGUMENT: a radius outside 1 .. VH_ESDF_MAX_RADIUS, an
+ * unknown `unknown`, a negative entry of dims, lo - radius or lo + dims + radius beyond int32 on an axis, both outputs
+ * NULL, a NULL or not 16-byte aligned workspace, workspace_bytes below what vh_esdf_workspace_bytes reports, more than
+ * 2^31 - 1 voxels.
+ * Diagnostics: vh_set_option(ctx, "esdf_launches", k) with k = 1..3 makes vh_esdf_lattice stop behind its first k launches,
+ * for timing (tools/esdf_time.py): it still returns VH_OK and then writes NO output.  The setting stays on the context until
+ * it is set back to 0; vh_esdf_lattice_host ignores it. */
+#define VH_ESDF_MAX_RADIUS       255
+#define VH_ESDF_UNKNOWN_KEEP     0
+#define VH_ESDF_UNKNOWN_FREE     1
+#define VH_ESDF_UNKNOWN_OCCUPIED 2
+#define VH_ESDF_FAR  INT32_MAX
+#define VH_ESDF_NONE INT32_MIN
+int vh_esdf_workspace_bytes(const int32_t dims[3], int32_t radius, uint64_t *bytes);
+int vh_esdf_lattice(vh_context *ctx, const int32_t lo[3], const int32_t dims[3], int32_t radius, int32_t unknown,
+                    void *d_workspace, uint64_t workspace_bytes,
+                    int32_t *d_dist2    /* dims[0]*dims[1]*dims[2], x fastest, the layout of vh_sample_lattice; or NULL */,
+                    float *d_distance   /* the same size, metres; or NULL (not both NULL) */);
+/* The same with HOST outputs and a workspace of its own for the duration of the call (synchronises): for the C++ facade, as
+ * vh_sample_sdf_host.  Not a hot path. */
+int vh_esdf_lattice_host(vh_context *ctx, const int32_t lo[3], const int32_t dims[3], int32_t radius, int32_t unknown,
+                         int32_t *h_dist2, float *h_distance);
+
 /* ------------------------------------------------------------------ */
 /* the model met by rays                                               */
 /* ------------------------------------------------------------------ */

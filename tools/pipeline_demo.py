@@ -11,7 +11,10 @@ load_snapshot + load_color resumes from.  --stream-radius R keeps only the block
 every frame a streaming.BlockStore moves the blocks beyond R to the host and those within 0.8 R back (vh_stream_out / vh_stream_in);
 at the end every stored block is streamed back in, so a mesh or snapshot holds the whole model.  R should exceed the depth range:
 a block the camera still sees beyond R is allocated again by the next frame and streamed out again, replacing its stored record.
-tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--snapshot out.vhsnap] [--stream-radius R]"""
+--esdf out.npy writes the Euclidean signed distance to the surface (metres, float32 [z, y, x]; vh_esdf_lattice) over the bounding
+box of the model's blocks, up to --esdf-radius voxels (default 16), unknown voxels kept unknown (NaN).
+tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--snapshot out.vhsnap] [--stream-radius R]
+                       [--esdf out.npy] [--esdf-radius R]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -39,6 +42,13 @@ STREAM_RADIUS = None
 if "--stream-radius" in argv:
     STREAM_RADIUS = float(argv[argv.index("--stream-radius") + 1])
     del argv[argv.index("--stream-radius"):argv.index("--stream-radius") + 2]
+ESDF, ESDF_RADIUS = None, 16
+if "--esdf-radius" in argv:
+    ESDF_RADIUS = int(argv[argv.index("--esdf-radius") + 1])
+    del argv[argv.index("--esdf-radius"):argv.index("--esdf-radius") + 2]
+if "--esdf" in argv:
+    ESDF = argv[argv.index("--esdf") + 1]
+    del argv[argv.index("--esdf"):argv.index("--esdf") + 2]
 N = int(argv[0]) if argv else 60
 gt = synth.camera_loop(500)[200:200 + N]
 prims = synth.room_primitives()
@@ -131,6 +141,19 @@ if MESH_INDEXED:
         dt = time.perf_counter() - t0
     mesh_io.save_ply(MESH_INDEXED, mv, mf, mn)
     print(f"mesh indexed: triangles={len(mf)} vertices={len(mv)} ({1e3 * dt:.1f} ms with download) -> {MESH_INDEXED}")
+if ESDF:
+    keys = table.allocated()["pos"].astype(np.int64)
+    lo = keys.min(0) * 8
+    dims = (keys.max(0) + 1) * 8 - lo
+    with torch.cuda.stream(stream):
+        t0 = time.perf_counter()
+        dist = table.esdf_lattice(lo, dims, ESDF_RADIUS).cpu().numpy()
+        dt = time.perf_counter() - t0
+    np.save(ESDF, dist)
+    known = ~np.isnan(dist)
+    print(f"esdf: lo={tuple(int(v) for v in lo)} dims={tuple(int(v) for v in dims)} radius {ESDF_RADIUS} voxels, "
+          f"{known.mean():.3f} of the voxels known, {np.isfinite(dist).mean():.3f} with a distance "
+          f"({1e3 * dt:.1f} ms with download) -> {ESDF}")
 if SNAPSHOT:
     table.save_snapshot(SNAPSHOT)
     print(f"snapshot -> {SNAPSHOT}")

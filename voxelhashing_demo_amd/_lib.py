@@ -19,6 +19,9 @@ SEM_PINHOLE = 1
 BUF_HASH_TABLE, BUF_COMPACT, BUF_SDF_BLOCKS, BUF_HEAP = 0, 1, 2, 3
 FREE_BLOCK = -1
 SAMPLE_NEAREST, SAMPLE_TRILINEAR = 0, 1
+ESDF_MAX_RADIUS = 255
+ESDF_UNKNOWN_KEEP, ESDF_UNKNOWN_FREE, ESDF_UNKNOWN_OCCUPIED = 0, 1, 2      # vh_esdf_lattice: what an unknown voxel counts as
+ESDF_FAR, ESDF_NONE = 2**31 - 1, -2**31            # d_dist2: nothing of the other class within the radius; an unknown voxel
 RAY_HIT, RAY_MISS, RAY_REFUSED = 1, 0, -1          # the status word of vh_cast_rays' d_voxels
 STREAM_BOX, STREAM_SPHERE = 0, 1                   # vh_stream_region.kind
 STREAM_PLACED, STREAM_PRESENT, STREAM_UNPLACED, STREAM_FOREIGN = 0, 1, 2, 3       # the per-record status of vh_stream_in
@@ -169,6 +172,9 @@ SIGNATURES = {
     "vh_sample_sdf": (C.c_int, [_vp, _i32, C.c_uint64, _vp, _vp, _vp, _vp]),
     "vh_sample_sdf_host": (C.c_int, [_vp, _i32, C.c_uint64, _fp, _fp, _fp, _fp]),
     "vh_sample_lattice": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _vp]),
+    "vh_esdf_workspace_bytes": (C.c_int, [C.POINTER(_i32), _i32, C.POINTER(C.c_uint64)]),
+    "vh_esdf_lattice": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _vp, C.c_uint64, _vp, _vp]),
+    "vh_esdf_lattice_host": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, C.POINTER(_i32), _fp]),
     "vh_cast_rays": (C.c_int, [_vp, C.c_uint64, _vp, _fp, _vp, _vp, _vp]),
     "vh_cast_rays_host": (C.c_int, [_vp, C.c_uint64, _fp, _fp, _fp, _fp, C.POINTER(_i32)]),
     "vh_deintegrate": (C.c_int, [_vp, _fp, _vp]),

@@ -172,6 +172,18 @@ void SDF_Hashtable::sampleSdf(const std::vector<float> &points, int mode, std::v
                              gradient ? gradient->data() : nullptr), "sampleSdf");
 }
 
+void SDF_Hashtable::esdfLattice(const int32_t lo[3], const int32_t dims[3], int radius, int unknown, std::vector<int32_t> *dist2,
+                                std::vector<float> *distance)
+{
+    uint64_t n = 1;
+    for (int a = 0; a < 3; ++a) n = n > (uint64_t)INT32_MAX ? n : n * (dims[a] > 0 ? (uint64_t)dims[a] : 0);
+    if (n > (uint64_t)INT32_MAX) n = 0;          // (the call refuses such a box)
+    if (dist2) dist2->assign(n, 0);
+    if (distance) distance->assign(n, 0.0f);
+    check(vh_esdf_lattice_host(ctx_, lo, dims, radius, unknown, dist2 ? dist2->data() : nullptr, distance ? distance->data() : nullptr),
+          "esdfLattice");
+}
+
 void SDF_Hashtable::castRays(const std::vector<float> &rays, const float *depthPlane, std::vector<float> &t, std::vector<float> *normals,
                              std::vector<int32_t> *voxels)
 {

@@ -248,6 +248,7 @@ struct vh_context {
     // vh_extract_mesh_indexed: scratch of its first call, kept
     DevBuf<uint32_t> meshWords;            // per listed block 512 words {vertex prefix << 7 | edge mask}, then the per-block vertex counts, then listPos[ptr >> 9]
     DevBuf<unsigned long long> meshVertexTotals;   // the vertex scan's tile totals, then {listed blocks, vertices, triangles}
+    int esdfLaunches = 0;                  // option "esdf_launches": diagnostics (tools/esdf_time.py), vh_esdf_lattice stops behind its first 1..3 launches (timing only: no result); 0 or 4 = all four
     MergeScratch merge;                    // vh_merge into this context: scratch of its first call, kept
     DevBuf<uint32_t> color;                // the colour volume (vh_api_color.hip): one word per voxel, of the first colour-fusing call, kept
     StreamScratch streaming;               // vh_stream_in, vh_stream_*_host: scratch of the first call, kept
@@ -603,6 +604,7 @@ static int ensure_candidates(vh_context *c, size_t need)
 #include "vh_api_model.hip"
 #include "vh_api_mesh.hip"
 #include "vh_api_sample.hip"
+#include "vh_api_esdf.hip"
 #include "vh_api_rays.hip"
 #include "vh_api_deintegrate.hip"
 #include "vh_api_merge.hip"

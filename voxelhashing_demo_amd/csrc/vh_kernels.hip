@@ -23,6 +23,8 @@
 //                      LDS, count -> scan -> emit (no counterpart in the reference)
 //   vh_sample.hip      the model as a distance field: sdf / weight / gradient at world points (one point per lane),
 //                      dense boxes of the voxel lattice (one workgroup pass per brick; no counterpart in the reference)
+//   vh_esdf.hip        the Euclidean distance to the surface on the lattice: bit planes of the classes, an exact capped
+//                      squared distance transform axis by axis (no counterpart in the reference)
 //   vh_rays.hip        the DDA raycast for arbitrary ray batches: one ray per lane through vh_raycast.hip's per-lane walk
 //                      (no counterpart in the reference)
 //   vh_track.hip       point-to-SDF camera tracking: the ICP's round with the trilinear sample of the model as residual and
@@ -59,6 +61,7 @@
 #include "vh_icp.hip"
 #include "vh_mesh.hip"
 #include "vh_sample.hip"
+#include "vh_esdf.hip"
 #include "vh_rays.hip"
 #include "vh_track.hip"
 #include "vh_merge.hip"

@@ -603,6 +603,49 @@ class SDFHashtable:
         self.sample_lattice_into(lo, dims, sdf, w)
         return (sdf, w) if weight else sdf
 
+    # ---- the Euclidean distance to the surface ----
+    def esdf_workspace_bytes(self, dims, radius: int) -> int:
+        """Bytes of workspace vh_esdf_lattice needs for a box of `dims` at `radius` (0 for an empty box)."""
+        d3, n = (C.c_int32 * 3)(*[int(v) for v in dims]), C.c_uint64(0)
+        L.check(self._lib.vh_esdf_workspace_bytes(d3, int(radius), C.byref(n)), "vh_esdf_workspace_bytes")
+        return int(n.value)
+
+    def esdf_lattice_into(self, lo, dims, radius: int, dist2, distance=None, unknown: int = L.ESDF_UNKNOWN_KEEP, workspace=None):
+        """vh_esdf_lattice into caller-owned device buffers of dims[0] * dims[1] * dims[2] elements, x fastest: dist2 (int32) or
+        None, distance (float32, metres) or None; workspace: a CUDA byte tensor of at least esdf_workspace_bytes(dims, radius)
+        bytes, 16-byte aligned (None: a torch byte tensor is allocated for this call and given back to torch's allocator once
+        the context's stream has passed the launches that use it: nothing is kept between calls, so a loop over many boxes
+        does better with a workspace of its own).  Asynchronous on the context's stream."""
+        lo3, d3 = (C.c_int32 * 3)(*[int(v) for v in lo]), (C.c_int32 * 3)(*[int(v) for v in dims])
+        own = workspace is None
+        if own:
+            import torch
+            with torch.cuda.device(self.device_index()):
+                workspace = torch.empty((max(self.esdf_workspace_bytes(dims, radius), 16),), dtype=torch.uint8, device="cuda")
+        L.check(self._lib.vh_esdf_lattice(self._h, lo3, d3, int(radius), int(unknown), _dev_ptr(workspace),
+                                          int(workspace.numel() * workspace.element_size()), _dev_ptr(dist2), _dev_ptr(distance)),
+                "vh_esdf_lattice")
+        if own:                                     # the launches are only queued: no reuse before the context's stream is past them
+            dev = self.device_index()
+            workspace.record_stream(torch.cuda.ExternalStream(self.stream_handle, device=dev) if self.stream_handle
+                                    else torch.cuda.default_stream(dev))
+        return dist2 if dist2 is not None else distance
+
+    def esdf_lattice(self, lo, dims, radius: int, unknown: int = L.ESDF_UNKNOWN_KEEP, distance: bool = True, dist2: bool = False):
+        """The Euclidean signed distance to the surface at the voxels lo <= g < lo + dims, up to `radius` voxels, as CUDA tensors
+        [dims[2], dims[1], dims[0]]: the distance in metres (float32; +-inf: nothing of the other class within the radius, NaN:
+        an unknown voxel) and / or the exact signed squared distance in voxels (int32; ESDF_FAR, ESDF_NONE); a tuple
+        (distance, dist2) when both are asked for."""
+        import torch
+        if not (distance or dist2):
+            raise ValueError("ask for distance, dist2 or both")
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        with torch.cuda.device(self.device_index()):
+            f = torch.empty(shape, dtype=torch.float32, device="cuda") if distance else None
+            d = torch.empty(shape, dtype=torch.int32, device="cuda") if dist2 else None
+        self.esdf_lattice_into(lo, dims, radius, d, f, unknown)
+        return (f, d) if distance and dist2 else f if distance else d
+
     # ---- the model met by rays (DESIGN.md 4.10) ----
     def cast_rays_into(self, rays, t, normals=None, voxels=None, depth_plane=None, n: int = None):
         """vh_cast_rays into caller-owned device buffers: rays [n, 8] float32 (origin, t_min, direction, t_max; 16-byte
