@@ -598,6 +598,20 @@ static int ensure_candidates(vh_context *c, size_t need)
     return VH_OK;
 }
 
+// A frame with an allocation band: up to one contender per pixel AND band key.  On a smooth surface the wave-level collapse
+// leaves a few thousand and the W*H records of the context suffice; on incoherent depth (every pixel a block of its own,
+// tests/test_gpu_incoherent.py: 64x64 pixels, 17 500 keys at a 10 cm band) they do not, and the frame drops keys the oracle
+// inserts.  So the list is sized for the band before the frame's first launch (once per context and band: it only grows).
+static int ensure_band_candidates(vh_context *c)
+{
+    if (!(c->fp.allocBand > 0.0f)) return VH_OK;
+    const size_t npix = (size_t)c->fp.width * c->fp.height;
+    size_t keys = kMaxBandSamples - 1;                                       // the DDA bands: the walk's step limit
+    if (!(c->fp.flags & (kFlagBandDda | kFlagBandRayDda)))
+        keys = 2 * (size_t)std::ceil(c->fp.allocBand / (4.0f * c->fp.voxelSize)) + 1;      // vh_alloc.hip: band_samples
+    return ensure_candidates(c, npix * keys);
+}
+
 // the rest of the C-ABI, by area (one translation unit)
 #include "vh_api_frame.hip"
 #include "vh_api_shard.hip"

@@ -143,6 +143,7 @@ extern "C" int vh_alloc_blocks(vh_context *c, const vh_float4 *verts, const vh_f
     c->allocEpoch = c->epochTotal;
     DeviceGuard guard(c->device);
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }
+    { const int brc = ensure_band_candidates(c); if (brc != VH_OK) return brc; }
     int rc = launch_alloc(c, VertexMap{reinterpret_cast<const float4 *>(verts), reinterpret_cast<const float4 *>(normals)});
     if (rc != VH_OK) return rc;
     VH_HIP(hipGetLastError());
@@ -532,6 +533,7 @@ template <class In, class Depth>
 static int run_frame(vh_context *c, const In &in, const Depth &depth)
 {
     int rc;
+    if ((rc = ensure_band_candidates(c)) != VH_OK) return rc;
     c->occupiedCounter = kCompactCount;
     if (pipeline_applies(c)) {
         rc = launch_pipelined(c, &in, pipe_is_sensor(in), pipe_k(in).v);
