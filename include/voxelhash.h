@@ -1089,6 +1089,10 @@ int vh_load_color(vh_context *ctx, const char *path);
  * placed + present + unplaced + foreign == n.  With d_colors the colour volume is created first.  The keys that are neither
  * foreign nor present go through the insertion path of vh_insert_bins as one key bin, one lock epoch per round, until none is
  * missing or a round allocates nothing (stats->rounds; the call synchronises between rounds).  The compact list is left empty.
+ * Which record is UNPLACED when room runs out is as free as the slot a key gets: with "overflow_list" a key whose home bucket is
+ * full takes a free slot behind it, so in a crowded table whether the last keys of a call (here and in vh_merge's allocation)
+ * still find one can depend on which keys the rounds served first.  Keys that each have a free slot in their own home bucket,
+ * the other keys of the call counted, are all placed whatever the order.
  *
  * Both calls work on shards and with "overflow_list"; view tables are refused (they own no blocks).  The _host forms take host
  * buffers, stage through device scratch the context keeps, and copy once each way; vh_stream_out_host sizes the scratch from the
@@ -1129,7 +1133,11 @@ int vh_dump_sdf_text(vh_context *ctx, const char *path);
  * allocated entry) and its restore into a context created with the same configuration;
  * fusing can continue after vh_load_snapshot as if never interrupted.  Both synchronise.
  * Snapshots do not carry colour: vh_load_snapshot clears the colour volume ("the model in colour").  A coloured model is
- * saved as the pair vh_save_snapshot + vh_save_color and resumed with vh_load_snapshot followed by vh_load_color. */
+ * saved as the pair vh_save_snapshot + vh_save_color and resumed with vh_load_snapshot followed by vh_load_color.
+ * vh_counters after a load: heap_counter, allocated_total, heap_exhausted and epoch are the saved context's; freed_total is
+ * allocated_total minus the allocated entries (the file does not carry it; that is its value at the save, so the pool accounting
+ * allocated_total - freed_total == allocated entries holds on); the other counters are 0.  What the compact list holds after a
+ * load, and after vh_clear_color, is not specified: the next frame or flatten makes it. */
 int vh_save_snapshot(vh_context *ctx, const char *path);
 int vh_load_snapshot(vh_context *ctx, const char *path);
 

@@ -153,6 +153,8 @@ def lib():
         L.vho_icp_align.restype = C.c_int
         L.vho_delete_blocks.argtypes = [C.c_void_p, ip, C.c_int]
         L.vho_delete_blocks.restype = C.c_int
+        L.vho_insert_blocks.argtypes = [C.c_void_p, ip, C.c_int]
+        L.vho_insert_blocks.restype = C.c_int
         L.vho_garbage_collect.argtypes = [C.c_void_p, C.c_float]
         L.vho_garbage_collect.restype = C.c_int
         L.vho_export_view.argtypes = [C.c_void_p, fp, C.c_float, C.c_float, C.c_void_p, C.c_int]
@@ -377,6 +379,13 @@ class OracleTable:
         if len(keys):
             k[:, :3] = np.asarray(keys, np.int32).reshape(-1, 3)
         return int(lib().vho_delete_blocks(self._h, k.ctypes.data_as(C.POINTER(C.c_int32)), len(keys)))
+
+    def insert_blocks(self, keys) -> int:
+        """Places every absent key of `keys` (in turn) with a zeroed block; returns how many were placed."""
+        k = np.zeros((len(keys), 4), np.int32)
+        if len(keys):
+            k[:, :3] = np.asarray(keys, np.int32).reshape(-1, 3)
+        return int(lib().vho_insert_blocks(self._h, k.ctypes.data_as(C.POINTER(C.c_int32)), len(keys)))
 
     def garbage_collect(self, sdf_threshold: float) -> int:
         return int(lib().vho_garbage_collect(self._h, float(sdf_threshold)))

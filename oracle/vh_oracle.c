@@ -1354,6 +1354,79 @@ int vho_delete_blocks(vho_table *t, const int32_t *keys, int n)
     return freed;
 }
 
+/* Insertion of blocks the caller hands over (vh_stream_in, vh_merge's allocation): no lock epoch and no contenders, so every
+ * key that has room is placed.  An absent key goes to the first free slot of its home bucket with a zeroed block from the heap;
+ * with the overflow list on and the home bucket full it goes to the front of the bucket's chain under insert_entry_overflow's
+ * rule (a free slot among the 9 behind the bucket's last slot, never another bucket's last slot, the chain no longer than the
+ * lookup loop reaches).  A key that is present is left alone; a key with neither a slot nor a block is refused.  Returns the
+ * number of keys placed; the compact list is empty afterwards. */
+int vho_insert_blocks(vho_table *t, const int32_t *keys, int n)
+{
+    const uint32_t bs = t->p.bucketSize, L = t->p.attachedLinkedListSize;
+    int placed = 0;
+    for (int k = 0; k < n; ++k) {
+        const int32_t *key = keys + 4 * (size_t)k;
+        const uint32_t hg = vho_hash(key[0], key[1], key[2], t->p.numBuckets);
+        if (hg < t->bucket_lo || hg >= t->bucket_hi) continue;
+        const uint32_t h = hg - t->bucket_lo;
+        const size_t start = (size_t)h * bs, last = start + bs - 1;
+        if (t->heap_counter < 0) continue;
+        int64_t first_empty = -1;
+        int present = 0;
+        for (uint32_t i = 0; i < bs; ++i) {
+            const vho_entry *e = &t->table[start + i];
+            if (key_at(e, key)) { present = 1; break; }
+            if (first_empty < 0 && e->ptr == VHO_FREE_BLOCK) first_empty = (int64_t)(start + i);
+        }
+        if (present) continue;
+        if (!t->overflow) {
+            if (first_empty < 0) continue;
+            vho_entry *e = &t->table[first_empty];
+            e->pos[0] = key[0]; e->pos[1] = key[1]; e->pos[2] = key[2];
+            e->offset = 0;
+            e->ptr = heap_pop(t) * 512;
+            ++placed;
+            continue;
+        }
+        if (find_overflow(t, key, h, NULL) >= 0) continue;
+        if (first_empty >= 0) {
+            vho_entry *e = &t->table[first_empty];                   /* (a free last slot has offset 0) */
+            e->pos[0] = key[0]; e->pos[1] = key[1]; e->pos[2] = key[2];
+            e->ptr = heap_pop(t) * 512;
+            ++placed;
+            continue;
+        }
+        size_t base, cn;
+        chain_segment(t, h, &base, &cn);
+        uint32_t links = 0;
+        int ended = 0;
+        size_t i = last;
+        for (uint32_t iter = 0; iter < L; ++iter) {
+            const vho_entry *curr = &t->table[i];
+            if (curr->offset == 0) { ended = 1; break; }
+            i = chain_slot(last, curr->offset, base, cn);
+            ++links;
+        }
+        if (!ended || links + 1 > L - 1 || L < 2) continue;
+        int64_t target = -1;
+        int32_t tj = 0;
+        for (int32_t j = 1; j < 10; ++j) {
+            const size_t s = chain_slot(last, j, base, cn);
+            if (s % bs == bs - 1) continue;
+            if (t->table[s].ptr == VHO_FREE_BLOCK) { target = (int64_t)s; tj = j; break; }
+        }
+        if (target < 0) continue;
+        vho_entry *e = &t->table[target];
+        e->pos[0] = key[0]; e->pos[1] = key[1]; e->pos[2] = key[2];
+        e->ptr = heap_pop(t) * 512;
+        e->offset = t->table[last].offset;
+        t->table[last].offset = tj;
+        ++placed;
+    }
+    t->compact_counter = 0;
+    return placed;
+}
+
 int vho_garbage_collect(vho_table *t, float sdf_threshold)
 {
     const int n = t->compact_counter;

@@ -127,6 +127,10 @@ void vho_render_blocks(const vho_table *t, const float pose[16], float t_min, fl
 /* ---- block deletion / garbage collection (build extension) ---- */
 int vho_delete_blocks(vho_table *t, const int32_t *keys /* n x {x,y,z,_} */, int n);
 int vho_garbage_collect(vho_table *t, float sdf_threshold);
+/* Blocks handed over (vh_stream_in, vh_merge's allocation): each absent key gets the first free slot of its home bucket, or a
+ * place on the bucket's chain with the overflow list on, and a zeroed block; returns the number placed (present keys and keys
+ * without a slot or a block are not).  Which heap block a key gets is not specified. */
+int vho_insert_blocks(vho_table *t, const int32_t *keys /* n x {x,y,z,_} */, int n);
 
 /* ---- raycast over shards (build extension): the blocks a view can
  * touch are gathered from the shards into a view table that raycasts like the whole ---- */

@@ -380,6 +380,8 @@ extern "C" int vh_load_snapshot(vh_context *c, const char *path)
     int32_t counters[kNumCounters] = {0};
     counters[kHeapCounter] = h.heapCounter;
     counters[kAllocatedTotal] = (int32_t)h.allocatedTotal;
+    // (the file does not carry freed_total; allocated_total - freed_total is the allocated entries, before the save and after the load)
+    counters[kFreedTotal] = (int32_t)(h.allocatedTotal - (uint32_t)h.numAllocated);
     counters[kHeapExhausted] = (int32_t)h.heapExhausted;
     if (ok && e == hipSuccess) e = hipMemcpy(c->dp.table, table.data(), sizeof(VoxelEntry) * table.size(), hipMemcpyHostToDevice);
     if (ok && e == hipSuccess) e = hipMemcpy(c->dp.heap, heap.data(), sizeof(uint32_t) * heap.size(), hipMemcpyHostToDevice);
