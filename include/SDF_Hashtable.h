@@ -103,6 +103,17 @@ public:
      * (+-inf, NaN); unknown = VH_ESDF_UNKNOWN_KEEP, _FREE or _OCCUPIED.  At least one of the two outputs.  Synchronises. */
     void esdfLattice(const int32_t lo[3], const int32_t dims[3], int radius, int unknown, std::vector<int32_t> *dist2,
                      std::vector<float> *distance);
+    /* The connected pieces of the model (vh_components, through host buffers): target = VH_COMPONENT_INSIDE (the valid voxels
+     * with sdf <= 0: what the mesh shows as closed pieces) or VH_COMPONENT_OUTSIDE, connectivity 6 or 14 (the mesh's own
+     * tetrahedra); region nullptr = the whole model.  components: one record per piece (global voxel of its root, size) in
+     * the rule's order; labels (optional, with lo and dims): for the voxels lo <= g < lo + dims, x fastest, the index of the
+     * voxel's piece or VH_COMPONENT_NONE.  Returns the stats.  Synchronises. */
+    vh_component_stats components(const vh_mesh_region *region, int target, int connectivity, std::vector<vh_component> &components,
+                                  const int32_t *lo = nullptr, const int32_t *dims = nullptr, std::vector<uint32_t> *labels = nullptr);
+    /* Takes every piece with fewer than minSize nodes out of the volume (vh_remove_components): voxels {0, 0}, colour 0, the
+     * blocks that emptied freed.  Returns the stats.  Synchronises. */
+    vh_component_stats removeComponents(uint64_t minSize, const vh_mesh_region *region = nullptr, int target = VH_COMPONENT_INSIDE,
+                                        int connectivity = 14);
     /* Where rays meet the surface (vh_cast_rays, through host buffers): rays = 8 floats per ray (origin, t_min, direction, t_max,
      * the layout of vh_ray); depthPlane = four floats (one plane places the samples of all rays: row 2 of a pose's inverse gives
      * the raycast's depths) or nullptr (along each ray); t = one float per ray, NaN where there is no hit; normals (optional)

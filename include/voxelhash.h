@@ -1122,6 +1122,66 @@ int vh_stream_in_host(vh_context *ctx, uint64_t n, const vh_view_record *h_recor
                       vh_stream_stats *stats);
 
 /* ------------------------------------------------------------------ */
+/* connected pieces of the model                       */
+/* ------------------------------------------------------------------ */
+/* vh_components labels the connected pieces of the fused model; vh_remove_components takes the small ones out of the volume,
+ * so that every later vh_extract_mesh*, vh_raycast, vh_cast_rays and vh_esdf_lattice is free of them.  The rule is in
+ * integers: the GPU gives the bits of tests/components_ref.py.
+ *   Valid voxel.  vh_sample_sdf's rule: its block is allocated in this table (or shard), weight > 0, and its sdf is not NaN.
+ *   Nodes.  target VH_COMPONENT_INSIDE: the valid voxels with sdf <= 0 (the mesh's inside rule: -0.0, +0.0 and -inf are
+ *     inside), so a component is what the mesh shows as one closed piece.  VH_COMPONENT_OUTSIDE: the other valid voxels
+ *     (pockets and bubbles).  Only voxels of blocks inside `region` (NULL: the whole model) are nodes: a region boundary, an
+ *     absent block and a block of another shard all cut the graph.
+ *   Edges.  connectivity 6: nodes A and B are joined iff B - A = +-e for an axis unit vector e.  connectivity 14: iff
+ *     B - A = +-o for o in {0,1}^3 \ {0}: exactly the edges (A, d), d = 1..7, of the Kuhn split vh_extract_mesh_indexed
+ *     anchors at every voxel, so two inside voxels are joined iff the mesh's own tetrahedra join them.  (1, -1, 0) and its
+ *     kin are not edges.  There is no other connectivity, in particular no 26.
+ *   Identity and order.  A node's id is rank * 512 + voxel index: rank = the position of its block in the ordered block list
+ *     (ascending entry index, the mesh's order), voxel index = ((z&7)<<6)|((y&7)<<3)|(x&7).  A component's root is its node
+ *     of least id; components are output in ascending root id.  The same table gives the same bytes; the partition and the
+ *     multiset of sizes do not depend on the table at all.
+ *   Limit.  Ids fit a uint32 with VH_COMPONENT_NONE reserved: a region with more than 2^23 - 1 listed blocks returns
+ *     VH_ERR_INVALID_ARGUMENT; stats->blocks is reported, the other counts are 0 and nothing is written.
+ *
+ * vh_components writes the first `capacity` records, in order, and reports what the region holds even when that exceeds the
+ * capacity, as vh_extract_mesh does (capacity 0 with NULL buffers: the count-only call).  d_labels has vh_sample_lattice's
+ * layout over lo, dims: the index of the voxel's component in output order (it may be at or beyond `capacity`), or
+ * VH_COMPONENT_NONE where the voxel is no node.  stats: blocks listed, nodes, components and the largest component's size; the
+ * removal fields are 0.  The call runs on the context's stream behind every queued frame (a pending pipelined frame is
+ * launched first), synchronises once to return the stats, and changes nothing in the model.  It works on shards, on view
+ * tables and with or without "overflow_list".  Its scratch (one uint32 per voxel of the listed blocks, one word per pool block,
+ * eight words and a count per listed block) is allocated at the first call, grown on demand and kept; a context that never
+ * calls it allocates nothing for it.  VH_ERR_INVALID_ARGUMENT: an unknown target or connectivity, a capacity without a
+ * buffer, a box given in part (lo, dims and d_labels: all three or none), a box vh_sample_lattice refuses.
+ *
+ * vh_remove_components labels in the same way, then every node of a component with size < min_size becomes {0, 0}, as a
+ * de-integrated voxel does, and its colour word 0 where a colour volume exists.  A block in which the call cleared at least
+ * one voxel and whose 512 weights are then all 0 is freed through the deletion path of vh_delete_blocks, in a lock epoch of
+ * its own (vh_counters.last_freed / freed_total say what was freed; the compact list is left as vh_delete_blocks leaves it);
+ * blocks that were empty before are left alone.  min_size 0 or 1 removes nothing.  Removing is idempotent, and clearing
+ * whole components never splits another.  stats as above, of the labelling before the removal, plus the components and
+ * voxels removed and the blocks freed.  View tables are refused (they own no blocks).  The call synchronises.
+ * Diagnostics: vh_set_option(ctx, "components_launches", k) with k = 1..6 makes both calls stop behind the first k stages of
+ * the labelling (block list, local pass, seam pass, flatten, count, scan + records), for tools/components_time.py: such a
+ * call returns no result and removes nothing.  0 or 7: the whole call (the default). */
+#define VH_COMPONENT_INSIDE  0
+#define VH_COMPONENT_OUTSIDE 1
+#define VH_COMPONENT_NONE    0xFFFFFFFFu
+typedef struct vh_component { int32_t voxel[3]; uint32_t size; } vh_component;        /* 16 B: global voxel of the root, nodes */
+typedef struct vh_component_stats { uint64_t blocks, nodes, components, largest,      /* of the labelling */
+                                    removed_components, removed_voxels, freed_blocks; } vh_component_stats;
+
+int vh_components(vh_context *ctx, const vh_mesh_region *region /* NULL: whole model */, int32_t target, int32_t connectivity,
+                  uint64_t capacity, vh_component *d_components /* may be NULL when capacity is 0 */,
+                  const int32_t lo[3], const int32_t dims[3], uint32_t *d_labels /* all three NULL, or a lattice box */,
+                  vh_component_stats *stats /* host */);
+int vh_components_host(vh_context *ctx, const vh_mesh_region *region, int32_t target, int32_t connectivity, uint64_t capacity,
+                       vh_component *h_components, const int32_t lo[3], const int32_t dims[3], uint32_t *h_labels,
+                       vh_component_stats *stats);
+int vh_remove_components(vh_context *ctx, const vh_mesh_region *region, int32_t target, int32_t connectivity,
+                         uint64_t min_size, vh_component_stats *stats /* host, may be NULL */);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to

@@ -13,8 +13,11 @@ at the end every stored block is streamed back in, so a mesh or snapshot holds t
 a block the camera still sees beyond R is allocated again by the next frame and streamed out again, replacing its stored record.
 --esdf out.npy writes the Euclidean signed distance to the surface (metres, float32 [z, y, x]; vh_esdf_lattice) over the bounding
 box of the model's blocks, up to --esdf-radius voxels (default 16), unknown voxels kept unknown (NaN).
+--min-component N takes the floaters out before --mesh, --mesh-indexed, --esdf and --snapshot: every inside component (at
+connectivity 14, the mesh's own) with fewer than N voxels is cleared out of the volume and the blocks that emptied are freed
+(vh_remove_components); the stats are printed.
 tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--snapshot out.vhsnap] [--stream-radius R]
-                       [--esdf out.npy] [--esdf-radius R]"""
+                       [--esdf out.npy] [--esdf-radius R] [--min-component N]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -49,6 +52,10 @@ if "--esdf-radius" in argv:
 if "--esdf" in argv:
     ESDF = argv[argv.index("--esdf") + 1]
     del argv[argv.index("--esdf"):argv.index("--esdf") + 2]
+MIN_COMPONENT = 0
+if "--min-component" in argv:
+    MIN_COMPONENT = int(argv[argv.index("--min-component") + 1])
+    del argv[argv.index("--min-component"):argv.index("--min-component") + 2]
 N = int(argv[0]) if argv else 60
 gt = synth.camera_loop(500)[200:200 + N]
 prims = synth.room_primitives()
@@ -124,6 +131,14 @@ if store is not None:
     print(f"  streaming: radius {STREAM_RADIUS} m, {streamed['out']} blocks out and {streamed['back']} back during the loop, at most "
           f"{streamed['most']} on the host; at the end {left['placed']} restored, {left['present']} met a block allocated again "
           f"under their key meanwhile (kept in the store), {left['unplaced']} unplaced")
+if MIN_COMPONENT:
+    with torch.cuda.stream(stream):
+        t0 = time.perf_counter()
+        removed = table.remove_components(MIN_COMPONENT)
+        dt = time.perf_counter() - t0
+    print(f"components: blocks={removed['blocks']} inside voxels={removed['nodes']} components={removed['components']} "
+          f"largest={removed['largest']}; below {MIN_COMPONENT} voxels: {removed['removed_components']} components, "
+          f"{removed['removed_voxels']} voxels removed, {removed['freed_blocks']} blocks freed ({1e3 * dt:.1f} ms)")
 if MESH:
     from voxelhashing_demo_amd import mesh_io
     with torch.cuda.stream(stream):

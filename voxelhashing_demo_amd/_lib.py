@@ -23,6 +23,7 @@ ESDF_MAX_RADIUS = 255
 ESDF_UNKNOWN_KEEP, ESDF_UNKNOWN_FREE, ESDF_UNKNOWN_OCCUPIED = 0, 1, 2      # vh_esdf_lattice: what an unknown voxel counts as
 ESDF_FAR, ESDF_NONE = 2**31 - 1, -2**31            # d_dist2: nothing of the other class within the radius; an unknown voxel
 RAY_HIT, RAY_MISS, RAY_REFUSED = 1, 0, -1          # the status word of vh_cast_rays' d_voxels
+COMPONENT_INSIDE, COMPONENT_OUTSIDE, COMPONENT_NONE = 0, 1, 0xFFFFFFFF      # vh_components: target; the label of a voxel that is no node
 STREAM_BOX, STREAM_SPHERE = 0, 1                   # vh_stream_region.kind
 STREAM_PLACED, STREAM_PRESENT, STREAM_UNPLACED, STREAM_FOREIGN = 0, 1, 2, 3       # the per-record status of vh_stream_in
 
@@ -102,6 +103,15 @@ class StreamStats(C.Structure):
     """vh_stream_stats."""
     _fields_ = [("placed", C.c_uint64), ("present", C.c_uint64), ("unplaced", C.c_uint64), ("foreign", C.c_uint64),
                 ("rounds", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class ComponentStats(C.Structure):
+    """vh_component_stats."""
+    _fields_ = [(n, C.c_uint64) for n in ("blocks", "nodes", "components", "largest", "removed_components", "removed_voxels",
+                                          "freed_blocks")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -202,6 +212,11 @@ SIGNATURES = {
     "vh_stream_out_host": (C.c_int, [_vp, C.POINTER(StreamRegion), C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64)]),
     "vh_stream_in_host": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, C.POINTER(StreamStats)]),
+    "vh_components": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, _vp, C.POINTER(_i32), C.POINTER(_i32), _vp,
+                                C.POINTER(ComponentStats)]),
+    "vh_components_host": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, _vp, C.POINTER(_i32), C.POINTER(_i32), _vp,
+                                     C.POINTER(ComponentStats)]),
+    "vh_remove_components": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, C.POINTER(ComponentStats)]),
     "vh_sdf_build_system": (C.c_int, [_vp, _vp, _vp, _fp, _f, C.POINTER(IcpSystem)]),
     "vh_sdf_residuals": (C.c_int, [_vp, _vp, _vp, _fp, _f, _vp, _vp, _vp, C.POINTER(IcpSystem)]),
     "vh_sdf_align": (C.c_int, [_vp, _vp, _vp, _f, C.c_int32, C.POINTER(C.c_double), C.POINTER(IcpSystem), C.POINTER(C.c_int32)]),

@@ -184,6 +184,31 @@ void SDF_Hashtable::esdfLattice(const int32_t lo[3], const int32_t dims[3], int 
           "esdfLattice");
 }
 
+vh_component_stats SDF_Hashtable::components(const vh_mesh_region *region, int target, int connectivity,
+                                             std::vector<vh_component> &components, const int32_t *lo, const int32_t *dims,
+                                             std::vector<uint32_t> *labels)
+{
+    vh_component_stats st{};
+    check(vh_components_host(ctx_, region, target, connectivity, 0, nullptr, nullptr, nullptr, nullptr, &st), "components (count)");
+    components.assign((size_t)st.components, vh_component{});
+    const bool box = lo && dims && labels;
+    if (box) {
+        uint64_t n = 1;
+        for (int a = 0; a < 3; ++a) n = n > (uint64_t)INT32_MAX ? n : n * (dims[a] > 0 ? (uint64_t)dims[a] : 0);
+        labels->assign(n > (uint64_t)INT32_MAX ? 0 : (size_t)n, VH_COMPONENT_NONE);
+    }
+    check(vh_components_host(ctx_, region, target, connectivity, components.size(), components.empty() ? nullptr : components.data(),
+                             box ? lo : nullptr, box ? dims : nullptr, box ? labels->data() : nullptr, &st), "components");
+    return st;
+}
+
+vh_component_stats SDF_Hashtable::removeComponents(uint64_t minSize, const vh_mesh_region *region, int target, int connectivity)
+{
+    vh_component_stats st{};
+    check(vh_remove_components(ctx_, region, target, connectivity, minSize, &st), "removeComponents");
+    return st;
+}
+
 void SDF_Hashtable::castRays(const std::vector<float> &rays, const float *depthPlane, std::vector<float> &t, std::vector<float> *normals,
                              std::vector<int32_t> *voxels)
 {

@@ -165,6 +165,14 @@ struct StreamScratch {
     DevBuf<int32_t> hostStatus;            // vh_stream_in_host: the statuses on their way back
 };
 
+// vh_components / vh_remove_components (vh_api_components.hip): scratch of the first call, kept and grown on demand
+struct ComponentScratch {
+    DevBuf<uint32_t> parent;               // one word per voxel of the listed blocks: the union-find, then root (a root's word: root + size)
+    DevBuf<uint32_t> rank;                 // list position of the block whose ptr >> 9 is the index (heap blocks lie 512 voxels apart, view records 514)
+    DevBuf<unsigned long long> rootBits;   // per listed block 8 words: one bit per root; then the CompWord[] stats of the call
+    DevBuf<int4> keys;                     // vh_remove_components: the keys of the blocks that emptied
+};
+
 struct vh_context {
     HashTableParams params;
     FrameParams fp;
@@ -249,9 +257,11 @@ struct vh_context {
     DevBuf<uint32_t> meshWords;            // per listed block 512 words {vertex prefix << 7 | edge mask}, then the per-block vertex counts, then listPos[ptr >> 9]
     DevBuf<unsigned long long> meshVertexTotals;   // the vertex scan's tile totals, then {listed blocks, vertices, triangles}
     int esdfLaunches = 0;                  // option "esdf_launches": diagnostics (tools/esdf_time.py), vh_esdf_lattice stops behind its first 1..3 launches (timing only: no result); 0 or 4 = all four
+    int componentsLaunches = 0;            // option "components_launches": diagnostics (tools/components_time.py), vh_components stops behind its first 1..6 stages (timing only: no result); 0 or 7 = all
     MergeScratch merge;                    // vh_merge into this context: scratch of its first call, kept
     DevBuf<uint32_t> color;                // the colour volume (vh_api_color.hip): one word per voxel, of the first colour-fusing call, kept
     StreamScratch streaming;               // vh_stream_in, vh_stream_*_host: scratch of the first call, kept
+    ComponentScratch components;           // vh_components, vh_remove_components: scratch of the first call, kept
 };
 
 struct DeviceGuard {
@@ -628,3 +638,4 @@ static int ensure_band_candidates(vh_context *c)
 #include "vh_api_track.hip"
 #include "vh_api_dist.hip"
 #include "vh_api_stream.hip"
+#include "vh_api_components.hip"

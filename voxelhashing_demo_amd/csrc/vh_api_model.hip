@@ -490,6 +490,7 @@ extern "C" int vh_set_option(vh_context *c, const char *name, int value)
     if (std::strcmp(name, "commit_blocks") == 0 && value > 0) { c->commitBlocks = value; return VH_OK; }
     if (std::strcmp(name, "mesh_variant") == 0 && (value == 0 || value == 1)) { c->meshVariant = value; return VH_OK; }
     if (std::strcmp(name, "esdf_launches") == 0 && value >= 0 && value <= 4) { c->esdfLaunches = value; return VH_OK; }
+    if (std::strcmp(name, "components_launches") == 0 && value >= 0 && value <= 7) { c->componentsLaunches = value; return VH_OK; }
     return fail(VH_ERR_INVALID_ARGUMENT, "unknown option");
 }
 

@@ -38,6 +38,9 @@
 //   vh_stream.hip      block streaming: the blocks of a region out of the model as records (ordered list, pack, the deletion
 //                      path) and records back in (classification, the bin insertion path, one placed record per key); no
 //                      counterpart in the reference
+//   vh_components.hip  connected pieces of the model: a union-find over the sparse blocks (in LDS inside a block, atomicMin on the
+//                      larger root across the seams), sizes, records and labels in root order, removal of the small pieces
+//                      through the deletion path (no counterpart in the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -67,3 +70,4 @@
 #include "vh_merge.hip"
 #include "vh_color.hip"
 #include "vh_stream.hip"
+#include "vh_components.hip"

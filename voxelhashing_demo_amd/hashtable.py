@@ -646,6 +646,51 @@ class SDFHashtable:
         self.esdf_lattice_into(lo, dims, radius, d, f, unknown)
         return (f, d) if distance and dist2 else f if distance else d
 
+    # ---- connected pieces of the model ----
+    COMPONENT_DTYPE = np.dtype([("voxel", "<i4", (3,)), ("size", "<u4")])          # vh_component
+    _COMPONENT_TARGETS = {"inside": L.COMPONENT_INSIDE, "outside": L.COMPONENT_OUTSIDE}
+
+    def _component_target(self, target):
+        return self._COMPONENT_TARGETS[target] if isinstance(target, str) else int(target)
+
+    def components_into(self, capacity: int, records, lo=None, dims=None, labels=None, region=None, target="inside",
+                        connectivity: int = 14) -> dict:
+        """vh_components into caller-owned device buffers: records [capacity] of COMPONENT_DTYPE's 16 bytes (None with capacity
+        0), labels dims[0] * dims[1] * dims[2] uint32 (or int32) over the box lo, dims, x fastest (all three None: no labels).
+        Returns the stats as a dict; `components` may exceed `capacity`.  Synchronises."""
+        lo3 = (C.c_int32 * 3)(*[int(v) for v in lo]) if lo is not None else None
+        d3 = (C.c_int32 * 3)(*[int(v) for v in dims]) if dims is not None else None
+        st = L.ComponentStats()
+        L.check(self._lib.vh_components(self._h, self._mesh_region(region), self._component_target(target), int(connectivity),
+                                        int(capacity), _dev_ptr(records), lo3, d3, _dev_ptr(labels), C.byref(st)), "vh_components")
+        return st.as_dict()
+
+    def components(self, region=None, target="inside", connectivity: int = 14, lattice=None):
+        """The connected pieces of the model: (records, labels, stats).  target "inside": the valid voxels with sdf <= 0, what the
+        mesh shows as closed pieces; "outside": the other valid voxels.  connectivity 6 or 14 (the mesh's own tetrahedra).
+        records: a numpy array of COMPONENT_DTYPE (global voxel of the root, size) in output order; labels: with lattice =
+        (lo, dims) a CUDA tensor [dims[2], dims[1], dims[0]] int32 holding each voxel's index into records, -1 (the bits of
+        COMPONENT_NONE) where the voxel is no node; else None; stats: a dict of vh_component_stats."""
+        import torch
+        count = self.components_into(0, None, region=region, target=target, connectivity=connectivity)["components"]
+        lo, dims = lattice if lattice is not None else (None, None)
+        with torch.cuda.device(self.device_index()):
+            rec = torch.empty((max(count, 1), 4), dtype=torch.int32, device="cuda")
+            lab = torch.empty((int(dims[2]), int(dims[1]), int(dims[0])), dtype=torch.int32, device="cuda") if lattice is not None else None
+        stats = self.components_into(count, rec if count else None, lo, dims, lab, region, target, connectivity)
+        if stats["components"] != count:
+            raise L.VoxelHashError(f"the model changed between the count ({count}) and the labelling ({stats['components']})")
+        records = rec[:count].cpu().numpy().view(self.COMPONENT_DTYPE).reshape(count)
+        return records, lab, stats
+
+    def remove_components(self, min_size: int, region=None, target="inside", connectivity: int = 14) -> dict:
+        """vh_remove_components: every component with fewer than `min_size` nodes is cleared out of the volume (voxels {0, 0},
+        colour 0), and the blocks that emptied are freed.  Returns the stats as a dict.  Synchronises."""
+        st = L.ComponentStats()
+        L.check(self._lib.vh_remove_components(self._h, self._mesh_region(region), self._component_target(target),
+                                               int(connectivity), int(min_size), C.byref(st)), "vh_remove_components")
+        return st.as_dict()
+
     # ---- the model met by rays (DESIGN.md 4.10) ----
     def cast_rays_into(self, rays, t, normals=None, voxels=None, depth_plane=None, n: int = None):
         """vh_cast_rays into caller-owned device buffers: rays [n, 8] float32 (origin, t_min, direction, t_max; 16-byte
