@@ -51,6 +51,11 @@ public:
      * rounds with this tracker's distance threshold; the table must use this tracker's stream.  For models fused with a
      * truncation of a few voxels.  Returns the rounds that took a step; lastError() is the summed residual.  Synchronises. */
     int AlignToModel(SDF_Hashtable &table, const vh_float4 *d_input, float4x4 &pose, int rounds = 10);
+    /* ... and against its colour as well (vh_sdf_color_align, voxelhash.h "tracking against the model's colour and shape"):
+     * d_rgba = the W*H colour image registered to the depth image the vertex map came from, one word per pixel.  A table
+     * without colour gives AlignToModel's result.  colorWeight 0.1 is the literature's value, not tuned on this model. */
+    int AlignToModelColor(SDF_Hashtable &table, const vh_float4 *d_input, const uint32_t *d_rgba, float4x4 &pose, int rounds = 10,
+                          float colorWeight = 0.1f, float colorThres = 0.2f);
     float lastError() const { return globalCorrespondenceError; }
 };
 

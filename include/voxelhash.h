@@ -859,6 +859,58 @@ int vh_fusion_step_sdf(vh_context *ctx, struct vh_icp *icp, const uint16_t *d_de
                        struct vh_icp_system *last, int32_t *iterations);
 
 /* ------------------------------------------------------------------ */
+/* tracking against the model's colour and shape                       */
+/* ------------------------------------------------------------------ */
+/* vh_sdf_align with a photometric row beside the geometric one: where the model holds colour ("the model in colour" below),
+ * the luminance it has at the moved point is compared with the luminance of the input pixel (Kerl et al., IROS 2013, against
+ * the fused colour volume instead of a key frame; tests/sdf_color_track_ref.py is the rule in executable
+ * form).  A flat wall, a floor or a table top leaves the geometric system singular in the plane; the texture on it does not.
+ * IEEE fp32, every multiply, add and divide rounded on its own, in the order written here.
+ *   Point, sample, geometric kept, geometric row: vh_sdf_align's -- q, (s, g), |s| < dist_thres and g finite, J = [g, q x g]
+ *     with residual s.
+ *   Luminance of a colour word w = r | g << 8 | b << 16 | ...: Y(w) = (float)(77 * r + 150 * g + 29 * b) / 65280.0f (the sum
+ *     is an integer; Y lies in 0..1).
+ *   Input intensity: I = Y(d_rgba[idx]), d_rgba the W x H colour image registered to the depth image (vh_integrate_color's
+ *     layout, one word per pixel; its top byte is ignored).
+ *   Model intensity at q: there is one iff vh_sample_color's VH_SAMPLE_TRILINEAR rule has a sample at q -- eight valid corners,
+ *     all eight words with a count > 0, a colour volume present.  C = the lerp nest of vh_sample_sdf (x innermost, then y,
+ *     then z) over the eight Y values; gC = the gradient vh_sample_sdf forms from corner differences, over those eight values,
+ *     divided by voxelSize.
+ *   Photometric residual e = C - I.  Photometric kept: the pixel is geometrically kept, q has a model intensity,
+ *     |e| < color_thres, and color_weight != 0.
+ *   Photometric row: h_a = color_weight * gC_a, J = [h, q x h], residual color_weight * e.
+ *   System: the sums of "tracking against the model itself" over all rows, geometric and photometric; count = the number of
+ *     rows, error = the sum of the rows' residuals.  Step, stop conditions, *iterations and *last as vh_sdf_align.
+ *   Maps (vh_sdf_color_residuals): d_points, d_sdf, d_gradient as vh_sdf_residuals; d_color_residual = e where the pixel has
+ *     a photometric row, else NaN; d_color_gradient = gC where it has one, else (0, 0, 0).
+ * Consequences: with color_weight == 0, on a context without a colour volume, or on a context that holds an imported view,
+ * every call returns the bits of the vh_sdf_* call -- pose, system, maps (d_color_residual all NaN, d_color_gradient all 0).
+ * On a shard the blocks of other shards are absent, as for vh_sample_color: a cell that reaches into one has no sample.
+ * color_weight: 0.1 is the value of the numpy prototype and of the literature (intensity in 0..1 against metres); it has not
+ * been tuned on this model.
+ * Stream, workspace, the one synchronising read-back and a pending pipelined frame: as vh_sdf_*.  vh_fusion_step_sdf_color is
+ * one tracked colour frame: vh_preprocess -> vh_sdf_color_align(start = pose) -> vh_integrate_depth_color((float)pose, ...,
+ * band, weight_max).
+ * VH_ERR_INVALID_ARGUMENT, and nothing is changed or launched: what vh_sdf_* refuses; a NULL d_rgba; a color_weight that is
+ * not finite or below 0; a color_thres that is not finite or not above 0; for vh_fusion_step_sdf_color what
+ * vh_integrate_depth_color refuses (band, weight_max, a view table). */
+int vh_sdf_color_build_system(vh_context *ctx, struct vh_icp *icp, const vh_float4 *d_input, const uint32_t *d_rgba,
+                              const float pose[16], float dist_thres, float color_weight, float color_thres,
+                              struct vh_icp_system *out);                                   /* synchronises */
+int vh_sdf_color_residuals(vh_context *ctx, struct vh_icp *icp, const vh_float4 *d_input, const uint32_t *d_rgba,
+                           const float pose[16], float dist_thres, float color_weight, float color_thres,
+                           float *d_points /* W*H*3 */, float *d_sdf /* W*H */, float *d_gradient /* W*H*3 */,
+                           float *d_color_residual /* W*H */, float *d_color_gradient /* W*H*3 */,
+                           struct vh_icp_system *out);                                      /* the same + the maps */
+int vh_sdf_color_align(vh_context *ctx, struct vh_icp *icp, const vh_float4 *d_input, const uint32_t *d_rgba, float dist_thres,
+                       float color_weight, float color_thres, int32_t max_iters,
+                       double pose[16] /* in: start; out: result */, struct vh_icp_system *last, int32_t *iterations);
+int vh_fusion_step_sdf_color(vh_context *ctx, struct vh_icp *icp, const uint16_t *d_depth, const float k_inv[9],
+                             const uint32_t *d_rgba, float dist_thres, float color_weight, float color_thres, int32_t max_iters,
+                             float band, int32_t weight_max, vh_float4 *d_input_vertices, vh_float4 *d_input_normals,
+                             double pose[16], struct vh_icp_system *last, int32_t *iterations);
+
+/* ------------------------------------------------------------------ */
 /* one model into another                                              */
 /* ------------------------------------------------------------------ */
 /* Merging: the TSDF held by src is fused into dst under the rigid transform src_to_dst -- submaps whose relative pose a loop

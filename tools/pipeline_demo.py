@@ -7,7 +7,9 @@ stage and the drift against the true trajectory; --mesh writes the fused model a
 (welded by position on the host), --mesh-indexed the indexed mesh the GPU makes (one vertex per cell edge).  --color fuses a
 synthetic colour image with every frame (vh_integrate_color_map, a band of three voxels); --snapshot writes the model at the end
 (vh_save_snapshot) and, where the model is coloured, its colour words beside it as <path>.color (vh_save_color): the pair
-load_snapshot + load_color resumes from.  --stream-radius R keeps only the blocks within R metres of the camera on the GPU: after
+load_snapshot + load_color resumes from.  --tracker sdf-color (with --color) takes the pose from the model's own distance field and
+colour instead of a raycast and the ICP (vh_sdf_color_align): the model is then fused with a truncation of three voxels, which
+that tracker is for, and the colour images are a texture fixed to the scene instead of noise.  --stream-radius R keeps only the blocks within R metres of the camera on the GPU: after
 every frame a streaming.BlockStore moves the blocks beyond R to the host and those within 0.8 R back (vh_stream_out / vh_stream_in);
 at the end every stored block is streamed back in, so a mesh or snapshot holds the whole model.  R should exceed the depth range:
 a block the camera still sees beyond R is allocated again by the next frame and streamed out again, replacing its stored record.
@@ -16,7 +18,8 @@ box of the model's blocks, up to --esdf-radius voxels (default 16), unknown voxe
 --min-component N takes the floaters out before --mesh, --mesh-indexed, --esdf and --snapshot: every inside component (at
 connectivity 14, the mesh's own) with fewer than N voxels is cleared out of the volume and the blocks that emptied are freed
 (vh_remove_components); the stats are printed.
-tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--snapshot out.vhsnap] [--stream-radius R]
+tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--tracker icp|sdf-color]
+                       [--snapshot out.vhsnap] [--stream-radius R]
                        [--esdf out.npy] [--esdf-radius R] [--min-component N]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,6 +40,12 @@ if "--mesh" in argv:
 COLOR = "--color" in argv
 if COLOR:
     argv.remove("--color")
+TRACKER = "icp"
+if "--tracker" in argv:
+    TRACKER = argv[argv.index("--tracker") + 1]
+    del argv[argv.index("--tracker"):argv.index("--tracker") + 2]
+if TRACKER not in ("icp", "sdf-color") or (TRACKER == "sdf-color" and not COLOR):
+    raise SystemExit("--tracker is icp or sdf-color, and sdf-color needs --color")
 SNAPSHOT = None
 if "--snapshot" in argv:
     SNAPSHOT = argv[argv.index("--snapshot") + 1]
@@ -66,7 +75,8 @@ depth16 = [(synth.render_room_verts(p, W, H, prims, device="cuda")[..., 2] * 500
            for p in gt]
 torch.cuda.synchronize()           # the sensor frames were made on torch's default stream
 stream = torch.cuda.Stream()
-table = V.SDFHashtable(V.default_params(numBuckets=1 << 20, numVoxelBlocks=1 << 16), W, H, V.SEM_PINHOLE, stream=stream)
+extra = dict(truncation=0.06) if TRACKER == "sdf-color" else {}
+table = V.SDFHashtable(V.default_params(numBuckets=1 << 20, numVoxelBlocks=1 << 16, **extra), W, H, V.SEM_PINHOLE, stream=stream)
 trk = tracking.CameraTracking(W, H, K, stream=stream, flags=tracking.ICP_ABS_DISTANCE | tracking.ICP_NEED_TARGET)
 verts, normals = torch.empty((H, W, 4), device="cuda"), torch.empty((H, W, 4), device="cuda")
 tp, tn = torch.empty_like(verts), torch.empty_like(verts)
@@ -82,7 +92,21 @@ if COLOR:
     stage["color"] = 0.0
     BAND = 3.0 * table.params.voxelSize
     paint = torch.Generator(device="cuda").manual_seed(1)
-    rgba = [torch.randint(0, 1 << 24, (H, W), dtype=torch.int32, device="cuda", generator=paint) for _ in range(N)]
+    if TRACKER == "sdf-color":
+        def textured(p):
+            """The colour image of pose p: a smooth texture of the world position each pixel sees."""
+            v = synth.render_room_verts(p, W, H, prims, device="cuda")
+            T = torch.as_tensor(np.asarray(p, np.float32).reshape(4, 4), device="cuda")
+            x, y, z = (v[..., :3] @ T[:3, :3].T + T[:3, 3]).unbind(-1)
+            r = 128 + 100 * torch.sin(7.0 * x + 3.0 * z + 0.3) * torch.cos(5.0 * y)
+            g = 128 + 100 * torch.sin(4.0 * x - 6.0 * y + 5.0 * z + 1.0)
+            b = 128 + 100 * torch.cos(6.5 * y - 0.7) * torch.cos(3.0 * x - 4.0 * z + 0.2)
+            r, g, b = (c.round().to(torch.int32) for c in (r, g, b))
+            return (r | (g << 8) | (b << 16)).contiguous()
+        rgba = [textured(p) for p in gt]
+        ctrk = tracking.SdfColorTracking(table, K=K, stream=stream)
+    else:
+        rgba = [torch.randint(0, 1 << 24, (H, W), dtype=torch.int32, device="cuda", generator=paint) for _ in range(N)]
     torch.cuda.synchronize()
 
 
@@ -99,7 +123,11 @@ errs = []
 with torch.cuda.stream(stream):
     for k in range(N):
         timed("preprocess", lambda: V.preprocess(depth16[k], kinv, verts, normals, stream=stream))
-        if k > 0:
+        if k > 0 and TRACKER == "sdf-color":
+            found = [None]
+            timed("align", lambda: found.__setitem__(0, ctrk.Align(verts, rgba[k], pose)))
+            pose = found[0].copy()
+        elif k > 0:
             def target():
                 table.raycast(pose.astype(np.float32), ray)
                 tracking.depth_to_maps(ray, kinv, tp, tn, stream=stream)

@@ -222,7 +222,13 @@ SIGNATURES = {
     "vh_sdf_align": (C.c_int, [_vp, _vp, _vp, _f, C.c_int32, C.POINTER(C.c_double), C.POINTER(IcpSystem), C.POINTER(C.c_int32)]),
     "vh_fusion_step_sdf": (C.c_int, [_vp, _vp, _vp, _fp, _f, C.c_int32, _vp, _vp, C.POINTER(C.c_double), C.POINTER(IcpSystem),
                                      C.POINTER(C.c_int32)]),
-    "vh_export_views": (C.c_int, [_vp, _fp, C.c_int32, _f, _f, _vp, C.c_int32, _vp]),
+    "vh_sdf_color_build_system": (C.c_int, [_vp, _vp, _vp, _vp, _fp, _f, _f, _f, C.POINTER(IcpSystem)]),
+    "vh_sdf_color_residuals": (C.c_int, [_vp, _vp, _vp, _vp, _fp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, C.POINTER(IcpSystem)]),
+    "vh_sdf_color_align": (C.c_int, [_vp, _vp, _vp, _vp, _f, _f, _f, C.c_int32, C.POINTER(C.c_double), C.POINTER(IcpSystem),
+                                     C.POINTER(C.c_int32)]),
+    "vh_fusion_step_sdf_color": (C.c_int, [_vp, _vp, _vp, _fp, _vp, _f, _f, _f, C.c_int32, _f, C.c_int32, _vp, _vp,
+                                           C.POINTER(C.c_double), C.POINTER(IcpSystem), C.POINTER(C.c_int32)]),
+    "vh_export_views":(C.c_int, [_vp, _fp, C.c_int32, _f, _f, _vp, C.c_int32, _vp]),
     "vh_import_view": (C.c_int, [_vp, _vp, C.c_int32]),
     "vh_synchronize": (C.c_int, [_vp]),
     "vh_get_counters": (C.c_int, [_vp, C.POINTER(Counters)]),

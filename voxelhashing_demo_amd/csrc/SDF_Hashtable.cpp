@@ -394,3 +394,17 @@ int CameraTracking::AlignToModel(SDF_Hashtable &table, const vh_float4 *d_input,
     globalCorrespondenceError = (float)last.error;
     return steps;
 }
+
+int CameraTracking::AlignToModelColor(SDF_Hashtable &table, const vh_float4 *d_input, const uint32_t *d_rgba, float4x4 &pose, int rounds,
+                                      float colorWeight, float colorThres)
+{
+    vh_icp_system last;
+    int steps = 0;
+    double T[16];
+    for (int i = 0; i < 16; ++i) T[i] = (double)pose.entries[i];
+    check(vh_sdf_color_align(table.context(), icp_, d_input, d_rgba, distThres_, colorWeight, colorThres, rounds, T, &last, &steps),
+          "AlignToModelColor");
+    for (int i = 0; i < 16; ++i) pose.entries[i] = (float)T[i];
+    globalCorrespondenceError = (float)last.error;
+    return steps;
+}

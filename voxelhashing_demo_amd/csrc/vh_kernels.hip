@@ -35,7 +35,9 @@
 //   vh_color.hip       the model in colour: a second volume of one word per voxel, the registered colour image fused into the
 //                      voxels near the surface in the TSDF update's launch shape and taken back out of them, colour at world
 //                      points with the sampler's shared look-ups (no counterpart in the reference)
-//   vh_stream.hip      block streaming: the blocks of a region out of the model as records (ordered list, pack, the deletion
+//   vh_track_color.hip camera tracking against the model's shape and colour: vh_track.hip's round with a photometric row, the
+//                      luminance of the cell's eight colour words against the input image (no counterpart in the reference)
+//   vh_stream.hip     block streaming: the blocks of a region out of the model as records (ordered list, pack, the deletion
 //                      path) and records back in (classification, the bin insertion path, one placed record per key); no
 //                      counterpart in the reference
 //   vh_components.hip  connected pieces of the model: a union-find over the sparse blocks (in LDS inside a block, atomicMin on the
@@ -69,5 +71,6 @@
 #include "vh_track.hip"
 #include "vh_merge.hip"
 #include "vh_color.hip"
+#include "vh_track_color.hip"
 #include "vh_stream.hip"
 #include "vh_components.hip"

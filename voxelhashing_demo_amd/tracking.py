@@ -307,3 +307,104 @@ class SdfFusionLoop:
 
     def close(self):
         self.trk.close()
+
+
+COLOR_WEIGHT = 0.1         # the prototype's and the literature's value (intensity 0..1 against metres); not tuned on this model
+COLOR_THRES = 0.2          # a fifth of the intensity range: an occlusion edge or a highlight is no photometric row
+
+
+class SdfColorTracking(SdfTracking):
+    """SdfTracking with a photometric row beside the geometric one (vh_sdf_color_*; include/voxelhash.h, "tracking against the
+    model's colour and shape"): SdfColorTracking(table); Align(input, rgba, start_pose) -> the camera -> world pose, with `rgba`
+    the uint32 [H, W] colour image registered to the depth image.  A table without a colour volume, a view table or
+    color_weight == 0 give SdfTracking's bits."""
+
+    def __init__(self, table, color_weight: float = COLOR_WEIGHT, color_thres: float = COLOR_THRES, K=None,
+                 dist_thres: float = DIST_THRES, max_iters: int = SDF_MAX_ITERS, width=None, height=None, stream=None):
+        super().__init__(table, K, dist_thres=dist_thres, max_iters=max_iters, width=width, height=height, stream=stream)
+        self.color_weight, self.color_thres = color_weight, color_thres
+
+    def build_system(self, inp, rgba, pose):
+        p = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        sys = L.IcpSystem()
+        L.check(self._lib.vh_sdf_color_build_system(self.table._h, self._h, _ptr(inp), _ptr(rgba), _fp(p), self.dist_thres,
+                                                    self.color_weight, self.color_thres, C.byref(sys)), "vh_sdf_color_build_system")
+        return system_arrays(sys)
+
+    def residuals(self, inp, rgba, pose, points, sdf, gradient, color_residual, color_gradient):
+        """The system, SdfTracking.residuals' three maps, and per pixel the photometric residual [H, W] (NaN without a
+        photometric row) and the luminance gradient [H, W, 3] (0 without one), in place."""
+        p = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(16))
+        sys = L.IcpSystem()
+        L.check(self._lib.vh_sdf_color_residuals(self.table._h, self._h, _ptr(inp), _ptr(rgba), _fp(p), self.dist_thres,
+                                                 self.color_weight, self.color_thres, _ptr(points), _ptr(sdf), _ptr(gradient),
+                                                 _ptr(color_residual), _ptr(color_gradient), C.byref(sys)), "vh_sdf_color_residuals")
+        return system_arrays(sys)
+
+    def Align(self, inp, rgba, start_pose):
+        """Up to max_iters joint rounds from `start_pose`; the result is kept in `pose`."""
+        p = np.ascontiguousarray(np.asarray(start_pose, np.float64).reshape(16)).copy()
+        sys, it = L.IcpSystem(), C.c_int32()
+        L.check(self._lib.vh_sdf_color_align(self.table._h, self._h, _ptr(inp), _ptr(rgba), self.dist_thres, self.color_weight,
+                                             self.color_thres, self.max_iters, _dp(p), C.byref(sys), C.byref(it)), "vh_sdf_color_align")
+        self.pose, self.last, self.iterations = p.reshape(4, 4), system_arrays(sys), int(it.value)
+        return self.pose
+
+
+class SdfColorFusionLoop:
+    """SdfFusionLoop for RGB-D frames: per uint16 depth image and uint32 colour image
+
+        vh_preprocess(depth)                          -> input vertex map
+        vh_sdf_color_align(input, rgba, start = pose) -> pose          (against the model's shape and colour as fused so far)
+        vh_integrate_depth_color(pose, depth, rgba)   -> the model takes the frame
+
+    all on the table's stream; the one host synchronisation of a frame is the Align's.  The first frame is integrated at
+    `start_pose`.  `band` and `weight_max` are vh_integrate_color's."""
+
+    def __init__(self, table, k_inv, band: float, weight_max: int = 255, color_weight: float = COLOR_WEIGHT,
+                 color_thres: float = COLOR_THRES, K=None, stream=None, dist_thres: float = DIST_THRES, max_iters: int = SDF_MAX_ITERS):
+        import torch
+        self.table, self.W, self.H = table, table.width, table.height
+        self.k_inv = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        self.band, self.weight_max = float(band), int(weight_max)
+        self.trk = SdfColorTracking(table, color_weight, color_thres, K, dist_thres=dist_thres, max_iters=max_iters, stream=stream)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.in_v, self.in_n = (torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev) for _ in range(2))
+        self.stream = self.trk.stream_handle
+        self.pose = None
+        self.frames = 0
+
+    def start(self, depth_u16, rgba, start_pose):
+        self.pose = np.asarray(start_pose, np.float64).reshape(4, 4).copy()
+        self.table.integrate_depth_color(self.pose.astype(np.float32), depth_u16, self.k_inv, rgba, self.band, self.weight_max)
+        self.frames = 1
+        return self.pose
+
+    def track(self, depth_u16, rgba):
+        """pre-process + Align only: the new pose (not yet integrated)."""
+        from .hashtable import preprocess
+        preprocess(depth_u16, self.k_inv, self.in_v, self.in_n, stream=self.stream)
+        self.pose = self.trk.Align(self.in_v, rgba, self.pose)
+        return self.pose
+
+    def fuse(self, depth_u16, rgba):
+        """integrate depth and colour at the current pose."""
+        self.table.integrate_depth_color(self.pose.astype(np.float32), depth_u16, self.k_inv, rgba, self.band, self.weight_max)
+        self.frames += 1
+
+    def step(self, depth_u16, rgba):
+        """track + fuse in one library call (vh_fusion_step_sdf_color)."""
+        sys, it = L.IcpSystem(), C.c_int32()
+        trk = self.trk
+        pose = np.ascontiguousarray(self.pose, np.float64).copy()
+        L.check(trk._lib.vh_fusion_step_sdf_color(self.table._h, trk._h, _ptr(depth_u16), _fp(self.k_inv), _ptr(rgba), trk.dist_thres,
+                                                  trk.color_weight, trk.color_thres, trk.max_iters, self.band, self.weight_max,
+                                                  _ptr(self.in_v), _ptr(self.in_n), _dp(pose.reshape(16)), C.byref(sys),
+                                                  C.byref(it)), "vh_fusion_step_sdf_color")
+        self.pose = trk.pose = pose
+        trk.last, trk.iterations = system_arrays(sys), int(it.value)
+        self.frames += 1
+        return self.pose
+
+    def close(self):
+        self.trk.close()
