@@ -636,7 +636,6 @@ static int ensure_band_candidates(vh_context *c)
 #include "vh_api_dropin.hip"
 #include "vh_api_icp.hip"
 #include "vh_api_track.hip"
-#include "vh_api_track_color.hip"
 #include "vh_api_dist.hip"
 #include "vh_api_stream.hip"
 #include "vh_api_components.hip"

@@ -1,7 +1,7 @@
 // vh_color.hip -- the model in colour: vh_integrate_color, vh_sample_color, the colour half of block deletion (DESIGN.md 4.14;
 // the rule: include/voxelhash.h, "the model in colour", and tests/color_ref.py).  No counterpart in the reference.
 // Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after vh_sample.hip (lane_cell comes from vh_integrate.hip,
-// sample_runs / sample_resolve / sample_voxel from vh_sample.hip).
+// sample_cell / sample_nearest_block / sample_voxel / cell_lerp from vh_sample.hip).
 //
 // Colour is a second volume beside dp.blocks, one uint32 per voxel at the same index: r | g << 8 | b << 16 | w << 24 with w the
 // sample count (1..255); the word 0 is "no colour".  It is not a member of DevPtrs (a by-value argument of every kernel, whose
@@ -143,8 +143,7 @@ struct ColorPoints {
     int toWorld;
 };
 
-// Lanes without a point stay in for the cross-lane reads of sample_runs / sample_resolve: no early return.  The corner walk of
-// the trilinear mode is sample_trilinear's (vh_sample.hip), restated because it needs the corners' block pointers.
+// Lanes without a point stay in for the cross-lane reads of sample_nearest_block / sample_cell (vh_sample.hip): no early return.
 __global__ __launch_bounds__(256) void color_points_kernel(const FrameParams fp, const DevPtrs dp, const uint32_t *__restrict__ color,
                                                            int mode, uint32_t n, const ColorPoints in, uint32_t *__restrict__ out)
 {
@@ -171,46 +170,17 @@ __global__ __launch_bounds__(256) void color_points_kernel(const FrameParams fp,
     uint32_t rgb = 0u;
 
     if (mode == kSampleNearest) {
-        int r[3] = {0, 0, 0};
-        if (inDomain) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) r[a] = f2i_rz(u[a] + __builtin_copysignf(0.5f, u[a]));
-        }
-        const int kx = r[0] >> 3, ky = r[1] >> 3, kz = r[2] >> 3;
-        const SampleRuns runs = sample_runs(lane, kx, ky, kz);
-        const int resolved = sample_resolve(fp, dp, lane, runs, inDomain, kx, ky, kz);
-        const uint32_t c = color_voxel(dp, color, inDomain ? resolved : VH_FREE_BLOCK, sample_index(r[0], r[1], r[2]));
+        const SampleNearest near = sample_nearest_block(fp, dp, lane, u, inDomain);
+        const uint32_t c = color_voxel(dp, color, near.ptr, sample_index(near.r[0], near.r[1], near.r[2]));
         if (c >> 24) rgb = (c & 0xffffffu) | 0xff000000u;
     } else {
-        int i[3] = {0, 0, 0};
-        float t[3] = {0.0f, 0.0f, 0.0f};
-        if (inDomain) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float f = __builtin_floorf(u[a]);
-                i[a] = f2i_rz(f);
-                t[a] = u[a] - f;
-            }
-        }
-        const int kx = i[0] >> 3, ky = i[1] >> 3, kz = i[2] >> 3;
-        const int cross = ((i[0] & 7) == 7 ? 1 : 0) | ((i[1] & 7) == 7 ? 2 : 0) | ((i[2] & 7) == 7 ? 4 : 0);
-        const SampleRuns runs = sample_runs(lane, kx, ky, kz);
-        int ptr[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int p = sample_resolve(fp, dp, lane, runs, inDomain && (c & ~cross) == 0, kx + (c & 1), ky + ((c >> 1) & 1),
-                                         kz + (c >> 2));
-            if ((c & ~cross) == 0) ptr[c] = p;
-            else if (c & ~cross & 1) ptr[c] = ptr[c & 6];
-            else if (c & ~cross & 2) ptr[c] = ptr[c & 5];
-            else ptr[c] = ptr[c & 3];
-        }
+        const SampleCell cell = sample_cell(fp, dp, lane, u, inDomain);
         uint32_t w[8];
         bool all = inDomain;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            w[c] = color_voxel(dp, color, inDomain ? ptr[c] : VH_FREE_BLOCK,
-                               sample_index(i[0] + (c & 1), i[1] + ((c >> 1) & 1), i[2] + (c >> 2)));
+            // (a lane without a point may hold the pointer of block (0, 0, 0): SampleCell::ptr)
+            w[c] = color_voxel(dp, color, inDomain ? cell.ptr[c] : VH_FREE_BLOCK, sample_cell_index(cell, c));
             all = all && (w[c] >> 24) != 0u;
         }
         if (all) {
@@ -220,9 +190,7 @@ __global__ __launch_bounds__(256) void color_points_kernel(const FrameParams fp,
                 float s[8];
 #pragma unroll
                 for (int c = 0; c < 8; ++c) s[c] = (float)((w[c] >> k) & 255u);
-                const float f = sample_lerp(sample_lerp(sample_lerp(s[0], s[1], t[0]), sample_lerp(s[2], s[3], t[0]), t[1]),
-                                            sample_lerp(sample_lerp(s[4], s[5], t[0]), sample_lerp(s[6], s[7], t[0]), t[1]), t[2]);
-                rgb |= (uint32_t)(f + 0.5f) << k;
+                rgb |= (uint32_t)(cell_lerp(s, cell.t) + 0.5f) << k;
             }
         }
     }

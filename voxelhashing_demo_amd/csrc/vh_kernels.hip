@@ -27,16 +27,15 @@
 //                      squared distance transform axis by axis (no counterpart in the reference)
 //   vh_rays.hip        the DDA raycast for arbitrary ray batches: one ray per lane through vh_raycast.hip's per-lane walk
 //                      (no counterpart in the reference)
-//   vh_track.hip       point-to-SDF camera tracking: the ICP's round with the trilinear sample of the model as residual and
-//                      its gradient as normal (no counterpart in the reference)
+//   vh_track.hip       camera tracking against the model itself: the ICP's round with the trilinear sample of the model as
+//                      residual and its gradient as normal, and the joint form with a photometric row, the luminance of the
+//                      cell's eight colour words against the input image (no counterpart in the reference)
 //   vh_merge.hip       one model fused into another under a rigid transform: candidate keys from the source's blocks through the
 //                      bin insertion path, then the TSDF update's launch shape with the distance-field sample as the measurement
 //                      (no counterpart in the reference); the same launch with src's colour carried along (vh_merge_color)
 //   vh_color.hip       the model in colour: a second volume of one word per voxel, the registered colour image fused into the
 //                      voxels near the surface in the TSDF update's launch shape and taken back out of them, colour at world
 //                      points with the sampler's shared look-ups (no counterpart in the reference)
-//   vh_track_color.hip camera tracking against the model's shape and colour: vh_track.hip's round with a photometric row, the
-//                      luminance of the cell's eight colour words against the input image (no counterpart in the reference)
 //   vh_stream.hip     block streaming: the blocks of a region out of the model as records (ordered list, pack, the deletion
 //                      path) and records back in (classification, the bin insertion path, one placed record per key); no
 //                      counterpart in the reference
@@ -71,6 +70,5 @@
 #include "vh_track.hip"
 #include "vh_merge.hip"
 #include "vh_color.hip"
-#include "vh_track_color.hip"
 #include "vh_stream.hip"
 #include "vh_components.hip"

@@ -144,41 +144,20 @@ __global__ __launch_bounds__(256) void merge_list_kernel(const FrameParams fp, c
     }
 }
 
-// The VH_SAMPLE_NEAREST sdf and weight at u, by vh_sample.hip's pieces in sample_points_kernel's order (that kernel goes on to
-// the gradient with the same runs and is left as it stands).  Called by every lane of the wave.
-__device__ __forceinline__ SampleVoxel merge_sample_nearest(const FrameParams &fp, const DevPtrs &dp, int lane, const float u[3],
-                                                            bool inDomain)
-{
-    int r[3] = {0, 0, 0};
-    if (inDomain) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) r[a] = f2i_rz(u[a] + __builtin_copysignf(0.5f, u[a]));
-    }
-    const int kx = r[0] >> 3, ky = r[1] >> 3, kz = r[2] >> 3;
-    const SampleRuns runs = sample_runs(lane, kx, ky, kz);
-    const int resolved = sample_resolve(fp, dp, lane, runs, inDomain, kx, ky, kz);
-    return sample_voxel(dp, inDomain ? resolved : VH_FREE_BLOCK, sample_index(r[0], r[1], r[2]));
-}
-
-// dst voxel (gx, gy, gz) <- the sample of src at Tinv * (g * vsDst); true: the voxel changed
-template <int kMode>
-__device__ __forceinline__ bool merge_voxel(const FrameParams &dst, const FrameParams &src, const DevPtrs &srcDp,
-                                            const MergeTransform &Tinv, int lane, int gx, int gy, int gz, float &sdfIO, float &wIO)
+// The point of src that dst voxel (gx, gy, gz) is sampled at, u = Tinv * (g * vsDst) / vsSrc; returns inDomain
+__device__ __forceinline__ bool merge_source_point(const FrameParams &dst, const FrameParams &src, const MergeTransform &Tinv, int gx,
+                                                   int gy, int gz, float u[3])
 {
     const float px = (float)gx * dst.voxelSize, py = (float)gy * dst.voxelSize, pz = (float)gz * dst.voxelSize;
-    float u[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) u[r] = merge_row(Tinv.m, r, px, py, pz) / src.voxelSize;
-    const bool inDomain = __builtin_fabsf(u[0]) < kSampleDomain && __builtin_fabsf(u[1]) < kSampleDomain &&
-                          __builtin_fabsf(u[2]) < kSampleDomain;          // false for NaN
-    float s, w;
-    if constexpr (kMode == kSampleNearest) {
-        const SampleVoxel v = merge_sample_nearest(src, srcDp, lane, u, inDomain);
-        s = v.sdf; w = v.weight;
-    } else {
-        const SampleTrilinear v = sample_trilinear(src, srcDp, lane, u, inDomain);
-        s = v.sdf; w = v.weight;
-    }
+    return __builtin_fabsf(u[0]) < kSampleDomain && __builtin_fabsf(u[1]) < kSampleDomain &&
+           __builtin_fabsf(u[2]) < kSampleDomain;                       // false for NaN
+}
+
+// src's sample (s, w) combined into a dst voxel; false: no sample, the voxel stays
+__device__ __forceinline__ bool merge_combine(const FrameParams &dst, float s, float w, float &sdfIO, float &wIO)
+{
     if (!(s == s) || !(w > 0.0f)) return false;
     s = (s >= 0.0f) ? __builtin_fminf(dst.truncation, s) : __builtin_fmaxf(-dst.truncation, s);
     const float os = sdfIO, ow = wIO;
@@ -190,6 +169,25 @@ __device__ __forceinline__ bool merge_voxel(const FrameParams &dst, const FrameP
         wIO = __builtin_fminf(dst.weightMax, ow + w);
     }
     return true;
+}
+
+// dst voxel (gx, gy, gz) <- the sample of src at its source point; true: the voxel changed.  Called by every lane of the wave.
+template <int kMode>
+__device__ __forceinline__ bool merge_voxel(const FrameParams &dst, const FrameParams &src, const DevPtrs &srcDp,
+                                            const MergeTransform &Tinv, int lane, int gx, int gy, int gz, float &sdfIO, float &wIO)
+{
+    float u[3];
+    const bool inDomain = merge_source_point(dst, src, Tinv, gx, gy, gz, u);
+    float s, w;
+    if constexpr (kMode == kSampleNearest) {
+        const SampleNearest n = sample_nearest_block(src, srcDp, lane, u, inDomain);
+        const SampleVoxel v = sample_voxel(srcDp, n.ptr, sample_index(n.r[0], n.r[1], n.r[2]));
+        s = v.sdf; w = v.weight;
+    } else {
+        const SampleTrilinear v = sample_trilinear(src, srcDp, sample_cell(src, srcDp, lane, u, inDomain), inDomain);
+        s = v.sdf; w = v.weight;
+    }
+    return merge_combine(dst, s, w, sdfIO, wIO);
 }
 
 // One block of dst's compact list per workgroup pass (the list is uniform across the workgroup, so every lane of every wave
@@ -229,71 +227,24 @@ __device__ __forceinline__ uint32_t merge_color_word(uint32_t c, uint32_t rgb, u
     return out;
 }
 
-// The VH_SAMPLE_TRILINEAR sdf, weight and colour at u.  The corner walk and the two lerp nests are sample_trilinear's
-// (vh_sample.hip), restated because the colour words need the corners' block pointers; the channels go one at a time over the
-// eight words so that no more than those stay live.  count == 0: no colour sample.  Called by every lane of the wave.
+// The VH_SAMPLE_TRILINEAR sdf, weight and colour at u: sample_trilinear's sdf and weight, and the colour words of the cell's
+// corners (vh_sample.hip), the channels one at a time over the eight words so that no more than those stay live.  count == 0:
+// no colour sample.  Called by every lane of the wave.
 struct MergeColorSample { float sdf, weight; uint32_t rgb, count; };
 
 __device__ __forceinline__ MergeColorSample merge_color_trilinear(const FrameParams &fp, const DevPtrs &dp,
                                                                   const uint32_t *__restrict__ color, int lane, const float u[3],
                                                                   bool inDomain)
 {
-    const float nan = __builtin_nanf("");
-    MergeColorSample r = {nan, 0.0f, 0u, 0u};
-    int i[3] = {0, 0, 0};
-    float t[3] = {0.0f, 0.0f, 0.0f};
-    if (inDomain) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float f = __builtin_floorf(u[a]);
-            i[a] = f2i_rz(f);
-            t[a] = u[a] - f;
-        }
-    }
-    const int kx = i[0] >> 3, ky = i[1] >> 3, kz = i[2] >> 3;
-    const int cross = ((i[0] & 7) == 7 ? 1 : 0) | ((i[1] & 7) == 7 ? 2 : 0) | ((i[2] & 7) == 7 ? 4 : 0);
-    const SampleRuns runs = sample_runs(lane, kx, ky, kz);
-    int ptr[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int p = sample_resolve(fp, dp, lane, runs, inDomain && (c & ~cross) == 0, kx + (c & 1), ky + ((c >> 1) & 1),
-                                     kz + (c >> 2));
-        if ((c & ~cross) == 0) ptr[c] = p;
-        else if (c & ~cross & 1) ptr[c] = ptr[c & 6];
-        else if (c & ~cross & 2) ptr[c] = ptr[c & 5];
-        else ptr[c] = ptr[c & 3];
-    }
-    SampleVoxel v[8];
-#pragma unroll
-    for (int c = 0; c < 8; c += 2) {
-        const int index = sample_index(i[0], i[1] + ((c >> 1) & 1), i[2] + (c >> 2));
-        if (!(cross & 1)) {
-            v[c] = v[c + 1] = SampleVoxel{nan, 0.0f};
-            if (ptr[c] != VH_FREE_BLOCK) {
-                const VoxelPair pair = *reinterpret_cast<const VoxelPair *>(dp.blocks + (size_t)ptr[c] + (size_t)index);
-                v[c] = sample_judge(pair.s0, pair.w0);
-                v[c + 1] = sample_judge(pair.s1, pair.w1);
-            }
-        } else {
-            v[c] = sample_voxel(dp, ptr[c], index);
-            v[c + 1] = sample_voxel(dp, ptr[c + 1], sample_index(i[0] + 1, i[1] + ((c >> 1) & 1), i[2] + (c >> 2)));
-        }
-    }
-    bool all = inDomain;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) all = all && v[c].sdf == v[c].sdf;
-    if (!all) return r;
-    const float tx = t[0], ty = t[1], tz = t[2];
-    r.sdf = sample_lerp(sample_lerp(sample_lerp(v[0].sdf, v[1].sdf, tx), sample_lerp(v[2].sdf, v[3].sdf, tx), ty),
-                        sample_lerp(sample_lerp(v[4].sdf, v[5].sdf, tx), sample_lerp(v[6].sdf, v[7].sdf, tx), ty), tz);
-    r.weight = sample_lerp(sample_lerp(sample_lerp(v[0].weight, v[1].weight, tx), sample_lerp(v[2].weight, v[3].weight, tx), ty),
-                           sample_lerp(sample_lerp(v[4].weight, v[5].weight, tx), sample_lerp(v[6].weight, v[7].weight, tx), ty), tz);
+    const SampleCell cell = sample_cell(fp, dp, lane, u, inDomain);
+    const SampleTrilinear t = sample_trilinear(fp, dp, cell, inDomain);
+    MergeColorSample r = {t.sdf, t.weight, 0u, 0u};
     if (!(r.weight > 0.0f)) return r;           // (no TSDF step, so no colour step: the words are not read)
-    // eight valid corners: every ptr names a block, inside src's colour volume as it is inside its SDF volume
+    // a sample, so eight valid corners: every ptr names a block, inside src's colour volume as it is inside its SDF volume
     uint32_t w[8], least = 255u;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        w[c] = color[(size_t)ptr[c] + (size_t)sample_index(i[0] + (c & 1), i[1] + ((c >> 1) & 1), i[2] + (c >> 2))];
+        w[c] = color[(size_t)cell.ptr[c] + (size_t)sample_cell_index(cell, c)];
         least = min(least, w[c] >> 24);
     }
     if (least == 0u) return r;
@@ -303,32 +254,22 @@ __device__ __forceinline__ MergeColorSample merge_color_trilinear(const FramePar
         float s[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) s[c] = (float)((w[c] >> k) & 255u);
-        const float f = sample_lerp(sample_lerp(sample_lerp(s[0], s[1], tx), sample_lerp(s[2], s[3], tx), ty),
-                                    sample_lerp(sample_lerp(s[4], s[5], tx), sample_lerp(s[6], s[7], tx), ty), tz);
-        r.rgb |= (uint32_t)(f + 0.5f) << k;
+        r.rgb |= (uint32_t)(cell_lerp(s, cell.t) + 0.5f) << k;
     }
     return r;
 }
 
-// the VH_SAMPLE_NEAREST form: merge_sample_nearest with the word beside the voxel
+// the VH_SAMPLE_NEAREST form: the voxel and the word beside it
 __device__ __forceinline__ MergeColorSample merge_color_nearest(const FrameParams &fp, const DevPtrs &dp,
                                                                 const uint32_t *__restrict__ color, int lane, const float u[3],
                                                                 bool inDomain)
 {
-    int r[3] = {0, 0, 0};
-    if (inDomain) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) r[a] = f2i_rz(u[a] + __builtin_copysignf(0.5f, u[a]));
-    }
-    const int kx = r[0] >> 3, ky = r[1] >> 3, kz = r[2] >> 3;
-    const SampleRuns runs = sample_runs(lane, kx, ky, kz);
-    const int resolved = sample_resolve(fp, dp, lane, runs, inDomain, kx, ky, kz);
-    const int ptr = inDomain ? resolved : VH_FREE_BLOCK;
-    const int index = sample_index(r[0], r[1], r[2]);
-    const SampleVoxel v = sample_voxel(dp, ptr, index);
+    const SampleNearest n = sample_nearest_block(fp, dp, lane, u, inDomain);
+    const int index = sample_index(n.r[0], n.r[1], n.r[2]);
+    const SampleVoxel v = sample_voxel(dp, n.ptr, index);
     MergeColorSample out = {v.sdf, v.weight, 0u, 0u};
     if (v.sdf == v.sdf) {                       // (a valid voxel: ptr names a block)
-        const uint32_t word = color[(size_t)ptr + (size_t)index];
+        const uint32_t word = color[(size_t)n.ptr + (size_t)index];
         out.rgb = word & 0xffffffu;
         out.count = word >> 24;
     }
@@ -341,27 +282,12 @@ __device__ __forceinline__ int merge_color_voxel(const FrameParams &dst, const F
                                                  const uint32_t *__restrict__ srcColor, const MergeTransform &Tinv, int lane,
                                                  uint32_t weightMax, int gx, int gy, int gz, float &sdfIO, float &wIO, uint32_t &cIO)
 {
-    const float px = (float)gx * dst.voxelSize, py = (float)gy * dst.voxelSize, pz = (float)gz * dst.voxelSize;
     float u[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) u[r] = merge_row(Tinv.m, r, px, py, pz) / src.voxelSize;
-    const bool inDomain = __builtin_fabsf(u[0]) < kSampleDomain && __builtin_fabsf(u[1]) < kSampleDomain &&
-                          __builtin_fabsf(u[2]) < kSampleDomain;          // false for NaN
+    const bool inDomain = merge_source_point(dst, src, Tinv, gx, gy, gz, u);
     MergeColorSample v;
     if constexpr (kMode == kSampleNearest) v = merge_color_nearest(src, srcDp, srcColor, lane, u, inDomain);
     else v = merge_color_trilinear(src, srcDp, srcColor, lane, u, inDomain);
-    float s = v.sdf;
-    const float w = v.weight;
-    if (!(s == s) || !(w > 0.0f)) return 0;
-    s = (s >= 0.0f) ? __builtin_fminf(dst.truncation, s) : __builtin_fmaxf(-dst.truncation, s);
-    const float os = sdfIO, ow = wIO;
-    if (!(ow > 0.0f)) {
-        sdfIO = s;
-        wIO = __builtin_fminf(dst.weightMax, w);
-    } else {
-        sdfIO = ((os * ow) + (s * w)) / (ow + w);                       // combineVoxel's form
-        wIO = __builtin_fminf(dst.weightMax, ow + w);
-    }
+    if (!merge_combine(dst, v.sdf, v.weight, sdfIO, wIO)) return 0;
     if (v.count == 0u) return 1;
     const uint32_t c = merge_color_word(cIO, v.rgb, v.count, weightMax);
     const int changed = c != cIO ? 3 : 1;

@@ -9,6 +9,8 @@
 //                                 x-edge inside a block are one 16-byte load.  (One lookup_block per voxel read and eight
 //                                 scalar loads, the form this one was measured against: DESIGN_LOG.md.)
 //   sample_lattice_kernel         one workgroup pass per 8^3 brick that meets the box: one lookup, two voxels per lane.
+// The trilinear cell (sample_cell, sample_cell_voxels, cell_lerp, cell_gradient) and the nearest lookup (sample_nearest_block)
+// are stated here once for every kernel that samples the model: vh_color.hip, vh_merge.hip and vh_track.hip call them.
 #pragma once
 
 namespace vh {
@@ -70,75 +72,137 @@ __device__ __forceinline__ int sample_resolve(const FrameParams &fp, const DevPt
     return __shfl(p, runs.head);
 }
 
-// The VH_SAMPLE_TRILINEAR sample at u = p / voxelSize (inDomain: |u| < 2^30 on every axis), stated once for sample_points_kernel
-// and sdf_round_kernel (vh_track.hip).  Called by every lane of the wave, with or without a point (inDomain false): the lanes
-// of a run share the look-ups, a point resolves the 1, 2, 4 or 8 distinct blocks of its cell only, and the two corners of
-// an x-edge inside a block are one 16-byte load.  No sample: {NaN, 0, NaN}.
-struct SampleTrilinear { float sdf, weight, g[3]; };
+// The cell of the VH_SAMPLE_TRILINEAR sample at u = p / voxelSize (inDomain: |u| < 2^30 on every axis) and the blocks of its
+// eight corners, stated once for every trilinear reader of the model: sample_trilinear, merge_color_trilinear (vh_merge.hip),
+// color_points_kernel (vh_color.hip) and the joint round (vh_track.hip).  Called by every lane of the wave, with or without a
+// point (inDomain false): the lanes of a run share the look-ups, and a point resolves the 1, 2, 4 or 8 distinct blocks of its
+// cell only.
+struct SampleCell {
+    int i[3];            // the voxel of corner 0; (0, 0, 0) where inDomain is false
+    float t[3];
+    int cross;           // bit a: the cell crosses a block face on axis a
+    // The block of corner c, VH_FREE_BLOCK where the table has none.  A lane without a point has the key (0, 0, 0) and sits in
+    // a run like any other: it holds that block's pointer whenever a lane of its run asked for the block, so ptr says nothing
+    // about inDomain.  Every caller gates on inDomain itself -- before it judges the voxels (sample_trilinear,
+    // merge_color_trilinear) or before it reads through ptr (color_points_kernel); the reads of sample_cell_voxels need no
+    // gate: a pointer that is not VH_FREE_BLOCK names a whole block.
+    int ptr[8];
+};
 
-__device__ __forceinline__ SampleTrilinear sample_trilinear(const FrameParams &fp, const DevPtrs &dp, int lane, const float u[3],
-                                                            bool inDomain)
+__device__ __forceinline__ SampleCell sample_cell(const FrameParams &fp, const DevPtrs &dp, int lane, const float u[3], bool inDomain)
 {
-    const float nan = __builtin_nanf("");
-    SampleTrilinear r = {nan, 0.0f, {nan, nan, nan}};
-    int i[3] = {0, 0, 0};
-    float t[3] = {0.0f, 0.0f, 0.0f};
+    SampleCell cell = {{0, 0, 0}, {0.0f, 0.0f, 0.0f}, 0, {}};
     if (inDomain) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const float f = __builtin_floorf(u[a]);
-            i[a] = f2i_rz(f);
-            t[a] = u[a] - f;
+            cell.i[a] = f2i_rz(f);
+            cell.t[a] = u[a] - f;
         }
     }
-    const int kx = i[0] >> 3, ky = i[1] >> 3, kz = i[2] >> 3;
+    const int kx = cell.i[0] >> 3, ky = cell.i[1] >> 3, kz = cell.i[2] >> 3;
     // which axes the cell crosses a block face on: corner c lies in block (key + (c & cross))
-    const int cross = ((i[0] & 7) == 7 ? 1 : 0) | ((i[1] & 7) == 7 ? 2 : 0) | ((i[2] & 7) == 7 ? 4 : 0);
+    const int cross = ((cell.i[0] & 7) == 7 ? 1 : 0) | ((cell.i[1] & 7) == 7 ? 2 : 0) | ((cell.i[2] & 7) == 7 ? 4 : 0);
+    cell.cross = cross;
     const SampleRuns runs = sample_runs(lane, kx, ky, kz);
-    int ptr[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         // 1, 2, 4 or 8 distinct blocks: a corner whose bits all cross is a block of its own, any other shares the block of
         // the corner without one of its non-crossing bits (resolved before it)
         const int p = sample_resolve(fp, dp, lane, runs, inDomain && (c & ~cross) == 0, kx + (c & 1), ky + ((c >> 1) & 1),
                                      kz + (c >> 2));
-        if ((c & ~cross) == 0) ptr[c] = p;
-        else if (c & ~cross & 1) ptr[c] = ptr[c & 6];
-        else if (c & ~cross & 2) ptr[c] = ptr[c & 5];
-        else ptr[c] = ptr[c & 3];
+        if ((c & ~cross) == 0) cell.ptr[c] = p;
+        else if (c & ~cross & 1) cell.ptr[c] = cell.ptr[c & 6];
+        else if (c & ~cross & 2) cell.ptr[c] = cell.ptr[c & 5];
+        else cell.ptr[c] = cell.ptr[c & 3];
     }
-    SampleVoxel v[8];
+    return cell;
+}
+
+__device__ __forceinline__ int sample_cell_index(const SampleCell &cell, int c)
+{
+    return sample_index(cell.i[0] + (c & 1), cell.i[1] + ((c >> 1) & 1), cell.i[2] + (c >> 2));
+}
+
+// The eight voxels of the cell, judged.  The two corners of an x-edge inside a block are one 16-byte load.  No cross-lane read.
+__device__ __forceinline__ void sample_cell_voxels(const DevPtrs &dp, const SampleCell &cell, SampleVoxel v[8])
+{
 #pragma unroll
     for (int c = 0; c < 8; c += 2) {
-        const int index = sample_index(i[0], i[1] + ((c >> 1) & 1), i[2] + (c >> 2));
-        if (!(cross & 1)) {
-            v[c] = v[c + 1] = SampleVoxel{nan, 0.0f};
-            if (ptr[c] != VH_FREE_BLOCK) {
-                const VoxelPair pair = *reinterpret_cast<const VoxelPair *>(dp.blocks + (size_t)ptr[c] + (size_t)index);
+        const int index = sample_cell_index(cell, c);
+        if (!(cell.cross & 1)) {
+            v[c] = v[c + 1] = SampleVoxel{__builtin_nanf(""), 0.0f};
+            if (cell.ptr[c] != VH_FREE_BLOCK) {
+                const VoxelPair pair = *reinterpret_cast<const VoxelPair *>(dp.blocks + (size_t)cell.ptr[c] + (size_t)index);
                 v[c] = sample_judge(pair.s0, pair.w0);
                 v[c + 1] = sample_judge(pair.s1, pair.w1);
             }
         } else {
-            v[c] = sample_voxel(dp, ptr[c], index);
-            v[c + 1] = sample_voxel(dp, ptr[c + 1], sample_index(i[0] + 1, i[1] + ((c >> 1) & 1), i[2] + (c >> 2)));
+            v[c] = sample_voxel(dp, cell.ptr[c], index);
+            v[c + 1] = sample_voxel(dp, cell.ptr[c + 1], sample_cell_index(cell, c + 1));
         }
     }
+}
+
+// the lerp nest (x innermost, then y, then z) and the corner-difference gradient over the eight values of a cell
+__device__ __forceinline__ float cell_lerp(const float s[8], const float t[3])
+{
+    return sample_lerp(sample_lerp(sample_lerp(s[0], s[1], t[0]), sample_lerp(s[2], s[3], t[0]), t[1]),
+                       sample_lerp(sample_lerp(s[4], s[5], t[0]), sample_lerp(s[6], s[7], t[0]), t[1]), t[2]);
+}
+
+__device__ __forceinline__ void cell_gradient(const float s[8], const float t[3], float voxelSize, float g[3])
+{
+    g[0] = sample_lerp(sample_lerp(s[1] - s[0], s[3] - s[2], t[1]), sample_lerp(s[5] - s[4], s[7] - s[6], t[1]), t[2]) / voxelSize;
+    g[1] = sample_lerp(sample_lerp(s[2] - s[0], s[3] - s[1], t[0]), sample_lerp(s[6] - s[4], s[7] - s[5], t[0]), t[2]) / voxelSize;
+    g[2] = sample_lerp(sample_lerp(s[4] - s[0], s[5] - s[1], t[0]), sample_lerp(s[6] - s[2], s[7] - s[3], t[0]), t[1]) / voxelSize;
+}
+
+// The VH_SAMPLE_TRILINEAR sample in a cell (sample_cell's, with the inDomain it was given).  No sample: {NaN, 0, NaN}.  No
+// cross-lane read.
+struct SampleTrilinear { float sdf, weight, g[3]; };
+
+__device__ __forceinline__ SampleTrilinear sample_trilinear(const FrameParams &fp, const DevPtrs &dp, const SampleCell &cell,
+                                                            bool inDomain)
+{
+    const float nan = __builtin_nanf("");
+    SampleTrilinear r = {nan, 0.0f, {nan, nan, nan}};
+    SampleVoxel v[8];
+    sample_cell_voxels(dp, cell, v);
     bool all = inDomain;
 #pragma unroll
     for (int c = 0; c < 8; ++c) all = all && v[c].sdf == v[c].sdf;
     if (all) {
-        const float tx = t[0], ty = t[1], tz = t[2];
-        const float s0 = v[0].sdf, s1 = v[1].sdf, s2 = v[2].sdf, s3 = v[3].sdf, s4 = v[4].sdf, s5 = v[5].sdf, s6 = v[6].sdf,
-                    s7 = v[7].sdf;
-        r.sdf = sample_lerp(sample_lerp(sample_lerp(s0, s1, tx), sample_lerp(s2, s3, tx), ty),
-                            sample_lerp(sample_lerp(s4, s5, tx), sample_lerp(s6, s7, tx), ty), tz);
-        r.weight = sample_lerp(sample_lerp(sample_lerp(v[0].weight, v[1].weight, tx), sample_lerp(v[2].weight, v[3].weight, tx), ty),
-                               sample_lerp(sample_lerp(v[4].weight, v[5].weight, tx), sample_lerp(v[6].weight, v[7].weight, tx), ty), tz);
-        r.g[0] = sample_lerp(sample_lerp(s1 - s0, s3 - s2, ty), sample_lerp(s5 - s4, s7 - s6, ty), tz) / fp.voxelSize;
-        r.g[1] = sample_lerp(sample_lerp(s2 - s0, s3 - s1, tx), sample_lerp(s6 - s4, s7 - s5, tx), tz) / fp.voxelSize;
-        r.g[2] = sample_lerp(sample_lerp(s4 - s0, s5 - s1, tx), sample_lerp(s6 - s2, s7 - s3, tx), ty) / fp.voxelSize;
+        float s[8], w[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) { s[c] = v[c].sdf; w[c] = v[c].weight; }
+        r.sdf = cell_lerp(s, cell.t);
+        r.weight = cell_lerp(w, cell.t);
+        cell_gradient(s, cell.t, fp.voxelSize, r.g);
     }
     return r;
+}
+
+// The VH_SAMPLE_NEAREST voxel of u and its block.  Called by every lane of the wave, with or without a point.
+struct SampleNearest {
+    int r[3];            // the voxel; (0, 0, 0) where inDomain is false
+    SampleRuns runs;     // of the voxel's block key, for a caller that goes on to its neighbours
+    int ptr;             // the block, VH_FREE_BLOCK where the table has none or inDomain is false
+};
+
+__device__ __forceinline__ SampleNearest sample_nearest_block(const FrameParams &fp, const DevPtrs &dp, int lane, const float u[3],
+                                                              bool inDomain)
+{
+    SampleNearest n = {{0, 0, 0}, {}, VH_FREE_BLOCK};
+    if (inDomain) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) n.r[a] = f2i_rz(u[a] + __builtin_copysignf(0.5f, u[a]));
+    }
+    const int kx = n.r[0] >> 3, ky = n.r[1] >> 3, kz = n.r[2] >> 3;
+    n.runs = sample_runs(lane, kx, ky, kz);
+    const int resolved = sample_resolve(fp, dp, lane, n.runs, inDomain, kx, ky, kz);
+    n.ptr = inDomain ? resolved : VH_FREE_BLOCK;        // (a lane without a sample may sit in a run that has one)
+    return n;
 }
 
 __global__ __launch_bounds__(256) void sample_points_kernel(const FrameParams fp, const DevPtrs dp, int mode, uint32_t n,
@@ -159,15 +223,10 @@ __global__ __launch_bounds__(256) void sample_points_kernel(const FrameParams fp
     float sdf = nan, weight = 0.0f, g[3] = {nan, nan, nan};
 
     if (mode == kSampleNearest) {
-        int r[3] = {0, 0, 0};
-        if (inDomain) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) r[a] = f2i_rz(u[a] + __builtin_copysignf(0.5f, u[a]));
-        }
-        const int kx = r[0] >> 3, ky = r[1] >> 3, kz = r[2] >> 3;
-        const SampleRuns runs = sample_runs(lane, kx, ky, kz);
-        const int resolved = sample_resolve(fp, dp, lane, runs, inDomain, kx, ky, kz);
-        const int ptr = inDomain ? resolved : VH_FREE_BLOCK;       // (a lane without a sample may sit in a run that has one)
+        const SampleNearest near = sample_nearest_block(fp, dp, lane, u, inDomain);
+        const int *r = near.r;
+        const int ptr = near.ptr, kx = r[0] >> 3, ky = r[1] >> 3, kz = r[2] >> 3;
+        const SampleRuns &runs = near.runs;
         const SampleVoxel here = sample_voxel(dp, ptr, sample_index(r[0], r[1], r[2]));
         sdf = here.sdf;
         weight = here.weight;
@@ -199,7 +258,7 @@ __global__ __launch_bounds__(256) void sample_points_kernel(const FrameParams fp
             if (!ok) g[0] = g[1] = g[2] = nan;
         }
     } else {
-        const SampleTrilinear r = sample_trilinear(fp, dp, lane, u, inDomain);
+        const SampleTrilinear r = sample_trilinear(fp, dp, sample_cell(fp, dp, lane, u, inDomain), inDomain);
         sdf = r.sdf;
         weight = r.weight;
 #pragma unroll
