@@ -376,6 +376,9 @@ int vh_debug_icp_layout(const struct vh_icp *icp, int32_t out[3]);
  *     "walk_nt"          non-temporal loads in the reference walk (default: on when the table exceeds the 256 MiB Infinity Cache)
  *     "walk_reverse"     1 (default): the reference walk sweeps the table forward in one launch and backward in the next, each tile on
  *                        the same XCD, so that the tail of a sweep is still in that XCD's L2; 0: always forward (same compact SET)
+ *     "claim_lead"       groups of 8 walk workgroups that run ahead of a launch's first claim tile (the head of the sweep is read while
+ *                        the L2s still hold it); -1 (default): by the host's rule in the pipelined launch, none in the two-launch
+ *                        frame; >= 0: that many in both, clamped to the launch (same table, voxels and compact SET)
  *     "integrate_grid", "commit_blocks"   workgroups of the TSDF update / of the commit phase in the two-launch frame
  *     "gen_frames_per_launch"  1..8 (default 4): frames of a batch one key-generation launch of vh_generate_keys*_batch takes
  *     "spin_limit"       polls a workgroup of a serialised one-launch frame waits for the pending commit phase (0: default)

@@ -232,6 +232,7 @@ struct vh_context {
     bool serialQueued = false;             // a serialised launch has been queued since the host last looked at kSpinTimeouts (check_spin_timeouts)
     uint32_t spinSeen = 0;                 // ... and what the counter read then
     bool serialFallback = false;           // a serialised launch has timed out (vh_counters.spin_timeouts): overflow-list frames take two launches from now on
+    int claimLead = -1;                    // option "claim_lead": groups of walk workgroups ahead of the claim window (-1: the host's rule, claim_lead())
     int debugSkipRoles = 0;                // diagnostics: roles of the pipelined launch that return at once (timing only; the model is wrong)
     int pipelineShards = 1;                // option "pipeline_shards": vh_apply_frames_batch runs a batch of B multi-camera frames as B + 1 launches (1) or B (2: the last frame's half stays pending across calls)
     void *multiFirstEvent = nullptr;       // hipEvent_t recorded behind the first launch of every vh_apply_frames_batch (vh_dist: the previous batch's packets are free)

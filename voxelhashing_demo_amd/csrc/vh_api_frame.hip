@@ -205,6 +205,35 @@ static uint32_t claim_span(const vh_context *c, uint32_t claimBlocks, uint32_t w
     return std::min(total, std::max<uint32_t>(claimBlocks + (walkBlocks ? 1u : 0u), (uint32_t)(share * total)));
 }
 
+// How many groups of walk workgroups run ahead of the claim window (vh_frame.hip: grouped_role).  With the alternating sweep
+// the first walk groups of a launch read what their XCD's 4 MiB L2 still holds of the previous sweep, and the claim tiles'
+// traffic among them takes part of that away: in process the reversal is worth 2.6 us to C2's walk alone and 1.5 us to the
+// whole launch (profiles/pipelined_roles_reverse_C2.txt).  So the claim window starts behind the groups whose tiles fill
+// the eight L2s once (4 MiB / 20 bytes / 1024 or 2048 entries a tile: 204 or 102 groups), at most a quarter of the walk, and
+// keeps its end.  Same process, launch us by lead in groups -- C2 (640 walk groups): 0 17.94, 64 17.11, 128 16.67, 192 16.65,
+// 256 16.93, 320 17.33, 400 17.64; C3 (2 560): 0 67.92, 128 67.76, 256 67.53, 512 67.86, 768 68.35, 1 024 69.26.  The rule
+// itself, another session (profiles/claim_lead_ab.txt): C2 17.52 -> 16.33 (160 groups; 128, 160 and 192 within one spread of
+// each other), C3 68.14 -> 67.81 (204 groups: twice the spread of its rounds).  The quarter is a cap for small tables, not a
+// measured optimum: C2 is the one workload it binds on.  The window's END moving out with the lead loses most of the gain
+// (an earlier session, C2, lead 128: 17.40 -> 16.88, against 16.22 with the end kept).
+// Option "claim_lead" >= 0: that many groups; -1 (default): this rule in the pipelined launch without band allocation, else
+// none (the two-launch frame and the loaded frame are not measured with a lead).
+static uint32_t claim_lead(const vh_context *c, uint32_t claimGroups, uint32_t walkGroups, uint32_t &span, bool pipelined)
+{
+    uint32_t want = 0u;
+    if (c->claimLead >= 0) want = (uint32_t)c->claimLead;
+    else if (pipelined && !(c->fp.allocBand > 0.0f)) {
+        const size_t tileBytes = sizeof(VoxelEntry) * kFlattenThreads * ((c->fp.flags & kFlagWalkShort) ? kEntriesPerLaneShort : kEntriesPerLane);
+        want = std::min<uint32_t>((uint32_t)(((size_t)4 << 20) / tileBytes), walkGroups / 4u);
+    }
+    // the window keeps the end claim_span gave it and starts `lead` groups in: span shrinks by the lead, and strictly more
+    // groups than claim groups stay in it (claim_ratio < 2^32)
+    const uint32_t least = claimGroups + (walkGroups ? 1u : 0u);
+    const uint32_t lead = span > least ? std::min(want, span - least) : 0u;
+    span -= lead;
+    return lead;
+}
+
 // ceil(claimBlocks * 2^32 / span): floor(r * ratio / 2^32) steps from 0 to claimBlocks in unit steps over r = 0 .. span
 static uint32_t claim_ratio(uint32_t claimBlocks, uint32_t span)
 {
@@ -399,7 +428,7 @@ static int launch_pipelined(vh_context *c, const In *in, int newSensor, const fl
     // C3 26.1 -> 25.1 us, while C2 prefers the 512 it has, 8.7 against 9.0)
     if (hasOld && a.walkIndexed && large) a.integrateBlocks *= 2u;
     a.numEntries = (uint32_t)c->numEntries;
-    a.walkGroups = 0u; a.walkReverse = 0u;
+    a.walkGroups = 0u; a.walkReverse = 0u; a.claimLead = 0u;
     uint32_t claimWalk = a.claimBlocks + a.walkBlocks;          // workgroups of the two roles
     if (a.walkIndexed) {
         a.claimSpan = claim_span(c, a.claimBlocks, a.walkBlocks);
@@ -414,6 +443,7 @@ static int launch_pipelined(vh_context *c, const In *in, int newSensor, const fl
         const uint32_t claimGroups = groups_of_8(a.claimBlocks);
         a.walkGroups = groups_of_8(a.walkBlocks);
         a.claimSpan = claim_span(c, claimGroups, a.walkGroups);
+        a.claimLead = claim_lead(c, claimGroups, a.walkGroups, a.claimSpan, true);       // (takes the lead off the span)
         a.claimRatio = claim_ratio(claimGroups, a.claimSpan);
         if (hasNew) a.walkReverse = take_walk_direction(c);
         claimWalk = 8u * (claimGroups + a.walkGroups);
@@ -502,14 +532,15 @@ static int launch_scan_claim(vh_context *c, const In &in, uint32_t claimBlocks, 
     if (kKind != kWalkIndexed) {
         // the reference's walk: both roles in groups of 8 workgroups (vh_frame.hip: grouped_role), span and ratio in groups
         const uint32_t claimGroups = groups_of_8(claimBlocks), walkGroups = groups_of_8(scanBlocks);
-        const uint32_t span = claim_span(c, claimGroups, walkGroups);
+        uint32_t span = claim_span(c, claimGroups, walkGroups);
+        const uint32_t lead = claim_lead(c, claimGroups, walkGroups, span, false);         // (takes the lead off the span)
         return launch(c, kPhaseFrameScanClaim, frame_scan_claim_kernel<kKind, In>, dim3(8u * (claimGroups + walkGroups)),
                       dim3(256), c->fp, c->dp, in, (uint32_t)c->numEntries, claimBlocks, c->fusedParity, planeOut,
-                      span, claim_ratio(claimGroups, span), walkGroups, take_walk_direction(c));
+                      span, claim_ratio(claimGroups, span), walkGroups, take_walk_direction(c), lead);
     }
     return launch(c, kPhaseFrameScanClaim, frame_scan_claim_kernel<kKind, In>, dim3(claimBlocks + scanBlocks),
                   dim3(256), c->fp, c->dp, in, (uint32_t)c->numEntries, claimBlocks, c->fusedParity, planeOut,
-                  claim_span(c, claimBlocks, scanBlocks), claim_ratio(claimBlocks, claim_span(c, claimBlocks, scanBlocks)), 0u, 0u);
+                  claim_span(c, claimBlocks, scanBlocks), claim_ratio(claimBlocks, claim_span(c, claimBlocks, scanBlocks)), 0u, 0u, 0u);
 }
 
 // the packed camera-z plane launch 1 leaves for launch 2 (vertex-map input only)

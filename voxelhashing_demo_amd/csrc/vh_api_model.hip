@@ -423,6 +423,7 @@ extern "C" int vh_set_option(vh_context *c, const char *name, int value)
         c->fp.flags = value ? (c->fp.flags | kFlagWalkShort) : (c->fp.flags & ~kFlagWalkShort);
         return VH_OK;
     }
+    if (std::strcmp(name, "claim_lead") == 0 && value >= -1) { c->claimLead = value; return VH_OK; }     // (groups; clamped to the grid at the launch)
 #ifdef VH_DEBUG_SKIP_ROLES      // diagnostics builds only (make EXTRA=-DVH_DEBUG_SKIP_ROLES): the check costs the product launch a scalar load per workgroup
     if (std::strcmp(name, "debug_skip_roles") == 0 && value >= 0 && value < 32) {
         c->debugSkipRoles = value;

@@ -31,11 +31,13 @@ namespace vh {
 // has had ceil(claimBlocks / 8) claims (claimRatio * claimSpan exceeds that many steps by less than claimSpan / 2^32).
 // Returns true for a claim workgroup (index: its claim tile, to be tested against claimBlocks), false for a walk
 // workgroup (index: its ordinal).
+// claimLead: the claim window starts that many groups into the grid, [claimLead, claimLead + claimSpan) -- the groups ahead of
+// it walk, with no claim before them (g below is the group's index inside the window; ahead of it the subtraction wraps).
 __device__ __forceinline__ bool grouped_role(uint32_t r, uint32_t claimBlocks, uint32_t claimSpan, uint32_t claimRatio,
-                                             uint32_t &index)
+                                             uint32_t claimLead, uint32_t &index)
 {
-    const uint32_t g = r >> 3, q = r & 7u;
-    uint32_t before = (claimBlocks + 7u) >> 3;
+    const uint32_t g = (r >> 3) - claimLead, q = r & 7u;
+    uint32_t before = (int32_t)g < 0 ? 0u : (claimBlocks + 7u) >> 3;
     if (g < claimSpan) {
         const unsigned long long phase = (unsigned long long)q << 29;          // q / 8 of a step
         before = (uint32_t)(((unsigned long long)g * claimRatio + phase) >> 32);
@@ -52,11 +54,12 @@ template <int kKind, class In>
 __global__ __launch_bounds__(256) void frame_scan_claim_kernel(const FrameParams fp, const DevPtrs dp, const In in,
                                                                uint32_t numEntries, uint32_t claimBlocks,
                                                                int parity, float *__restrict__ planeOut, uint32_t claimSpan,
-                                                               uint32_t claimRatio, uint32_t walkGroups, uint32_t walkReverse)
+                                                               uint32_t claimRatio, uint32_t walkGroups, uint32_t walkReverse,
+                                                               uint32_t claimLead)
 {
     if constexpr (kKind != kWalkIndexed) {
         uint32_t index;
-        if (grouped_role(blockIdx.x, claimBlocks, claimSpan, claimRatio, index)) {
+        if (grouped_role(blockIdx.x, claimBlocks, claimSpan, claimRatio, claimLead, index)) {
             if (index >= claimBlocks) return;
             __builtin_amdgcn_s_setprio(3);
             claim_tile(fp, dp, in, index, kFusedCand + parity, kNoPending, planeOut);
@@ -213,6 +216,7 @@ struct PipeArgs {
     uint32_t walkIndexed;                  // flatten_variant 4: the walk role runs over the bucket-occupancy bitmap
     uint32_t claimPerWave;                 // the claim role takes a launch tile per WAVE (claim_tile_wave; the walk-free builds only)
     uint32_t claimSpan, claimRatio;        // claim tiles are interleaved with the first walk tiles: over claimSpan groups of 8 workgroups (grouped_role)
+    uint32_t claimLead;                    // ... of which the first is group claimLead of the claim + walk workgroups
     uint32_t walkGroups, walkReverse;     // the reference's walk: its ordinals run over 8 * walkGroups >= walkBlocks, backward if walkReverse (vh_walk.hip: walk_tile)
     float *planeNew;                       // private depth copies written by claim(new) ...
     uint16_t *rawNew;
@@ -282,6 +286,11 @@ __device__ __forceinline__ void frame_pipelined(const FrameParams &fpNew, const 
     // the grid, where the walk drains (or commit first, integrate last) 21.5 / 105.9 against 21.0 / 94.6 for
     // this order on that box.  (Those orders were selectable at run time for a while; the run-time mapping
     // with its 64-bit divisions per workgroup cost every launch 2 us and is gone.)
+    // EVERY figure above predates the alternating sweep (vh_walk.hip: walk_tile): the first walk ordinals of a launch were
+    // not served from an XCD's L2 then, so it did not matter in that way what was dealt among them.  With the sweep, the
+    // role table (profiles/pipelined_roles_reverse_C2.txt) has the reversal win 2.6 us for the walk alone and 1.5 us for the
+    // whole launch; the claim role and the deferred half each take about half a microsecond of it back.  Hence the claim
+    // window's lead (grouped_role: claimLead); the order of the roles is as it was.
     const uint32_t b = blockIdx.x;
     uint32_t role, index;                          // 0 commit, 1 integrate, 2 claim, 3 walk
     if (b < a.commitBlocks) { role = 0; index = b; }
@@ -301,12 +310,20 @@ __device__ __forceinline__ void frame_pipelined(const FrameParams &fpNew, const 
         // the claim tiles are spread, in groups of 8, over the first a.claimSpan groups of the claim + walk workgroups
         // (grouped_role: multiply-high by a.claimRatio = ceil(claimGroups * 2^32 / claimSpan), no division in the kernel;
         // the host keeps a.commitBlocks + a.integrateBlocks a multiple of 8, so a walk ordinal = blockIdx mod 8)
-        const bool claims = grouped_role(b - a.commitBlocks - a.integrateBlocks, a.claimBlocks, a.claimSpan, a.claimRatio, index);
+        const bool claims = grouped_role(b - a.commitBlocks - a.integrateBlocks, a.claimBlocks, a.claimSpan, a.claimRatio, a.claimLead, index);
         role = claims ? 2u : 3u;
         if (claims && index >= a.claimBlocks) return;          // (fills up the last claim group)
     }
 #ifdef VH_DEBUG_SKIP_ROLES
-    if (a.skipRoles & (1u << role)) return;
+    if (a.skipRoles & (1u << role)) {
+        // (the commit role also clears the rotating counter sets: left uncleared, the lists a later mask's TSDF update reads grow
+        // over entries nobody wrote)
+        if (role == 0u && b == 0u && threadIdx.x == 0 && a.hasOld) {
+            clear_pipe_set(counters, a.setClear);
+            if (!a.hasNew) clear_pipe_set(counters, a.setNew);
+        }
+        return;
+    }
 #endif
     // first launch of a run (no frame in flight): nobody pops the heap during it, so its first workgroup
     // leaves the free-block count the NEXT launch will test frame i+1's insertions against
