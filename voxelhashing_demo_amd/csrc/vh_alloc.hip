@@ -226,6 +226,16 @@ struct SensorImage {
     }
 };
 
+// ... or a register: the lane's pixel as an earlier load_pixel returned it.  The pipelined launch requests a claim tile's
+// pixels first (that call also writes the private depth copy), reads what the probes need while they are in flight, and
+// then hands claim_tile the pixel in this form (vh_frame.hip: the claim role).  Same vertex, same validity, same keys.
+struct LoadedPixel {
+    float4 v, n;
+    __device__ __forceinline__ float4 normal(int) const { return n; }
+    __device__ __forceinline__ uint16_t raw(int) const { return 0; }
+    __device__ __forceinline__ float4 vertex(int, int, int) const { return v; }
+};
+
 __device__ __forceinline__ uint32_t num_tiles(const FrameParams &fp)
 {
     return (uint32_t)((fp.width + 15) >> 4) * (uint32_t)((fp.height + 15) >> 4);

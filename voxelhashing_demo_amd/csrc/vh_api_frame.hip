@@ -42,6 +42,9 @@ static inline uint32_t host_num_tiles(const vh_context *c)
 constexpr size_t kMaxTimedLaunches = 8192;
 static int accumulate_times(vh_context *c);
 
+// (-Wpsabi: the pipelined launch hands on a 64-byte vector by value, vh_frame.hip: PipeLeadWords)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpsabi"
 template <typename K, typename... Args>
 static int launch(vh_context *c, int phase, K kernel, dim3 grid, dim3 block, Args... args)
 {
@@ -70,6 +73,7 @@ static int launch(vh_context *c, int phase, K kernel, dim3 grid, dim3 block, Arg
     c->timed.push_back(t);
     return VH_OK;
 }
+#pragma clang diagnostic pop
 
 template <class In>
 static int launch_alloc(vh_context *c, const In &in)
@@ -322,16 +326,17 @@ struct PipeRotation {
     int iNew, iOld, iClear;            // counter sets (0..2): filled by the new frame (c->pipeSet once it is pending), consumed, cleared by this launch
     DevPtrs dpOld, dpNew;
 };
-// ... and its part of the launch's argument block (PipeArgs / MultiPipeArgs)
-template <class Args>
-static PipeRotation pipe_rotation(const vh_context *c, Args &a, bool hasNew, bool hasOld)
+// ... and its part of the launch's argument block (PipeArgs / MultiPipeArgs); which frames the launch carries goes where the
+// kernel reads it: `lead` is the single-camera launch's PipeLead, the multi-camera launch's MultiPipeArgs itself
+template <class Args, class Lead>
+static PipeRotation pipe_rotation(const vh_context *c, Args &a, Lead &lead, bool hasNew, bool hasOld)
 {
     PipeRotation r;
     r.oldParity = c->pipeParity; r.newParity = r.oldParity ^ 1;
     r.iOld = c->pipeSet; r.iNew = (r.iOld + 1) % 3; r.iClear = (r.iNew + 1) % 3;
     r.dpNew = pipe_view(c, r.newParity); r.dpOld = pipe_view(c, r.oldParity);
     a.setNew = kPipeSetStride * r.iNew; a.setOld = kPipeSetStride * r.iOld; a.setClear = kPipeSetStride * r.iClear;
-    a.hasNew = hasNew; a.hasOld = hasOld;
+    lead.hasNew = hasNew; lead.hasOld = hasOld;
     a.doneTag = c->pend.doneTag;
     a.spinLimit = c->spinLimit ? c->spinLimit : kSpinLimitDefault;
     return r;
@@ -406,8 +411,10 @@ static int launch_pipelined(vh_context *c, const In *in, int newSensor, const fl
     if (!hasNew && !hasOld) return VH_OK;
     int rc;
     if (!hasOld && (rc = ensure_pipeline_buffers(c)) != VH_OK) return rc;
-    PipeArgs a;
-    const PipeRotation r = pipe_rotation(c, a, hasNew, hasOld);
+    PipeArgs args;
+    PipeLead a{};                                   // the leading piece: role map and the walk's two values (vh_frame.hip)
+    const PipeRotation r = pipe_rotation(c, args, a, hasNew, hasOld);
+    a.table = r.dpNew.table;
     const bool band = c->fp.allocBand > 0.0f;       // (the new frame's; the pending frame's claims are done)
     a.walkBlocks = hasNew ? walk_blocks(c) : 0u;
     a.walkIndexed = c->flattenVariant == kWalkIndexed ? 1u : 0u;
@@ -419,9 +426,9 @@ static int launch_pipelined(vh_context *c, const In *in, int newSensor, const fl
     const uint32_t flagsOld = hasOld ? c->pend.fp.flags : c->fp.flags;
     const bool large = host_num_tiles(c) > 2400u;
     int lean = lean_for(c, flagsOld, band, a.walkIndexed != 0u, false);
-    a.claimPerWave = (hasNew && large && (lean == kLeanIndexed || lean == kLeanIndexedNt)) ? 1u : 0u;
-    if (a.claimPerWave) lean = lean_for(c, flagsOld, band, true, true);
-    a.claimBlocks = !hasNew ? 0u : a.claimPerWave ? (host_num_tiles(c) + 3u) / 4u : host_num_tiles(c);
+    const bool claimPerWave = hasNew && large && (lean == kLeanIndexed || lean == kLeanIndexedNt);
+    if (claimPerWave) lean = lean_for(c, flagsOld, band, true, true);
+    a.claimBlocks = !hasNew ? 0u : claimPerWave ? (host_num_tiles(c) + 3u) / 4u : host_num_tiles(c);
     a.commitBlocks = hasOld ? (uint32_t)c->commitBlocks : 0u;
     a.integrateBlocks = hasOld ? (uint32_t)c->pipeIntegrateGrid : 0u;
     // (the walk-free frame of a large image: its TSDF update is on the critical path, not under a walk -- twice the workgroups:
@@ -448,23 +455,32 @@ static int launch_pipelined(vh_context *c, const In *in, int newSensor, const fl
         if (hasNew) a.walkReverse = take_walk_direction(c);
         claimWalk = 8u * (claimGroups + a.walkGroups);
     }
-    a.planeNew = (hasNew && !newSensor) ? c->planeBuf[r.newParity].get() : nullptr;
-    a.rawNew = (hasNew && newSensor) ? c->rawBuf[r.newParity].get() : nullptr;
-    a.filter = c->claimFilter;
-    a.filtNew = kPendFilterWords * (uint32_t)r.iNew; a.filtOld = kPendFilterWords * (uint32_t)r.iOld;
-    a.filtClear = kPendFilterWords * (uint32_t)r.iClear;
+    args.planeNew = (hasNew && !newSensor) ? c->planeBuf[r.newParity].get() : nullptr;
+    args.rawNew = (hasNew && newSensor) ? c->rawBuf[r.newParity].get() : nullptr;
+    args.filter = c->claimFilter;
+    args.filtNew = kPendFilterWords * (uint32_t)r.iNew; args.filtOld = kPendFilterWords * (uint32_t)r.iOld;
+    args.filtClear = kPendFilterWords * (uint32_t)r.iClear;
 #ifdef VH_DEBUG_SKIP_ROLES
     a.skipRoles = (uint32_t)c->debugSkipRoles;
 #endif
     const dim3 grid(a.commitBlocks + a.integrateBlocks + claimWalk);
     In inNew{};
     if (hasNew) inNew = *in;
+    // A lean build is told that both frames' flags are its own (vh_frame.hip: role_arguments).  lean_for is what makes that
+    // true; a first launch, which has no pending frame, hands over the new frame's parameters in its place.  Checked here,
+    // where a drift between lean_for and lean_build would otherwise be undefined behaviour on the device.
+    const FrameParams &fpOld = hasOld ? c->pend.fp : c->fp;
+    if (lean != kLeanNone && (c->fp.flags != lean_build(lean).flags || fpOld.flags != lean_build(lean).flags))
+        return fail(VH_ERR_INVALID_ARGUMENT, "launch_pipelined: the lean build does not match the frames' flags");
+    // (the two kernel arguments are built as the members of the struct that states the kernel's parameter list)
     if (hasOld && c->pend.sensor) {
         const DepthSensor d{c->rawBuf[r.oldParity], c->pend.k[0], c->pend.k[1], c->pend.k[2], c->pend.k[3]};
-        rc = launch_pipelined_build<In, DepthSensor>(c, lean, band, serial, grid, c->fp, r.dpNew, inNew, c->pend.fp, r.dpOld, d, a);
+        const PipeSignature<In, DepthSensor> sig{__builtin_bit_cast(PipeLeadWords, a), {c->fp, r.dpNew, inNew, fpOld, r.dpOld, d, args}};
+        rc = launch_pipelined_build<In, DepthSensor>(c, lean, band, serial, grid, sig.lead, sig.rest);
     } else {
         const DepthPlane d{c->planeBuf[r.oldParity], 1};
-        rc = launch_pipelined_build<In, DepthPlane>(c, lean, band, serial, grid, c->fp, r.dpNew, inNew, c->pend.fp, r.dpOld, d, a);
+        const PipeSignature<In, DepthPlane> sig{__builtin_bit_cast(PipeLeadWords, a), {c->fp, r.dpNew, inNew, fpOld, r.dpOld, d, args}};
+        rc = launch_pipelined_build<In, DepthPlane>(c, lean, band, serial, grid, sig.lead, sig.rest);
     }
     if (rc != VH_OK) return rc;
     pipe_launched(c, r, serial, hasNew ? PendingFrame::kSingle : PendingFrame::kNone, hasOld, true, false);     // (run_frame counts the frame)

@@ -386,7 +386,7 @@ static int launch_multi_pipelined(vh_context *c, const MultiBatch *mb, int b, co
     uint32_t *maskOf[2] = {c->dp.compactMask, c->maskBuf2};
     MultiPipeArgs a;
     std::memset(&a, 0, sizeof a);
-    PipeRotation r = pipe_rotation(c, a, doNew, hasOld);
+    PipeRotation r = pipe_rotation(c, a, a, doNew, hasOld);
     a.numEntries = (uint32_t)c->numEntries;
     a.numCams = doNew ? mb->numCams : pend.numCams;
     a.packetStride = doNew ? mb->packetStride : pend.packetStride;

@@ -206,28 +206,43 @@ __global__ __launch_bounds__(256) void frame_commit_integrate_kernel(const Frame
 // (Round 3 measured the slimmer argument block the round-2 review asked for -- one FrameParams, one DevPtrs, and of the
 // pending frame only its inverse pose, lock epoch and three alternating pointers: 0.55 instead of 0.8 KB, scalar spills
 // 173-208 -> 129-137 -- side by side with this form on one box (tools/ab_commits.sh): C2 18.6 vs 18.0 us, C3 70.6 vs
-// 70.3, C2 with band allocation 24.1 vs 23.9.  Slower, so the two-struct form stays; the spills sit in the role
-// prologues, outside every loop.)
-struct PipeArgs {
-    uint32_t claimBlocks, walkBlocks, commitBlocks, integrateBlocks;
-    uint32_t numEntries;
-    int32_t setNew, setOld, setClear;      // counter sets: filled, consumed, cleared by this launch
-    uint32_t hasNew, hasOld;               // first launch of a run: no old frame; flush launch: no new frame
-    uint32_t walkIndexed;                  // flatten_variant 4: the walk role runs over the bucket-occupancy bitmap
-    uint32_t claimPerWave;                 // the claim role takes a launch tile per WAVE (claim_tile_wave; the walk-free builds only)
+// 70.3, C2 with band allocation 24.1 vs 23.9.  Slower, so the two-struct form stays.  That experiment changed the block's
+// SIZE; what a workgroup pays is the ORDER in which it reads the block -- see PipeLead.)
+//
+// The leading 64 bytes of the launch's arguments: what the role map needs and what a walk workgroup's loads need, so that ONE
+// wide scalar load and one wait stand between a workgroup's start and its role, and a walk workgroup issues its whole stream
+// (walk_load_tile) without reading anything else.  Everything behind it -- the two FrameParams, the two DevPtrs, PipeArgs --
+// is read inside the role that uses it, where it is used.  (Until this form the kernel took both FrameParams by value and
+// patched their flags for the lean builds: two structs live across every role, so every workgroup loaded and spilled both,
+// piece by piece with a full wait each, and read the three counter words behind `live`, before it looked at its role --
+// 17 scalar waits, 48 lane spills and a device-memory read ahead of a walk workgroup's first ptr load; DESIGN_LOG.md.)
+// The kernel receives it as one 16-dword vector, so the load is one instruction whatever the compiler makes of the rest.
+struct PipeLead {
+    uint32_t commitBlocks, integrateBlocks, claimBlocks, walkBlocks;
     uint32_t claimSpan, claimRatio;        // claim tiles are interleaved with the first walk tiles: over claimSpan groups of 8 workgroups (grouped_role)
     uint32_t claimLead;                    // ... of which the first is group claimLead of the claim + walk workgroups
-    uint32_t walkGroups, walkReverse;     // the reference's walk: its ordinals run over 8 * walkGroups >= walkBlocks, backward if walkReverse (vh_walk.hip: walk_tile)
+    uint32_t walkGroups, walkReverse;      // the reference's walk: its ordinals run over 8 * walkGroups >= walkBlocks, backward if walkReverse (vh_walk.hip: walk_tile)
+    uint32_t numEntries;
+    uint32_t hasNew, hasOld;               // first launch of a run: no old frame; flush launch: no new frame
+    uint32_t walkIndexed;                  // flatten_variant 4: the walk role runs over the bucket-occupancy bitmap
+    uint32_t skipRoles;                    // diagnostics build (VH_DEBUG_SKIP_ROLES, option "debug_skip_roles"): bit r set = workgroups of role r
+                                           // (0 commit, 1 integrate, 2 claim, 3 walk) return at once: what the launch costs without them; else 0
+    const VoxelEntry *table;               // = the new frame's DevPtrs::table
+};
+// (On the host the vector only travels by value between functions of this one translation unit, all built with the same
+// flags, so the x86 note about its calling convention, -Wpsabi, has nothing to say: it is switched off around the two places
+// that hand the vector on, the kernel below and vh_api_frame.hip's launch().)
+typedef uint32_t PipeLeadWords __attribute__((ext_vector_type(16)));
+static_assert(sizeof(PipeLead) == sizeof(PipeLeadWords), "PipeLead is the one 64-byte scalar load at the head of the arguments");
+
+struct PipeArgs {
+    int32_t setNew, setOld, setClear;      // counter sets: filled, consumed, cleared by this launch
     float *planeNew;                       // private depth copies written by claim(new) ...
     uint16_t *rawNew;
     uint32_t *filter;                      // claim filters (vh_alloc.hip: pend_maybe), three of kPendFilterWords words
     uint32_t filtNew, filtOld, filtClear;  // word offsets of the filter the new frame fills / the pending frame filled / this launch clears
     int32_t doneTag;                       // overflow list: the pending frame's tag (lock epochs since creation), published when its commit phase ends
     uint32_t spinLimit;                    // ... and how many polls a workgroup waits for it (wait_commit_done)
-#ifdef VH_DEBUG_SKIP_ROLES
-    uint32_t skipRoles;                    // diagnostics build (option "debug_skip_roles"): bit r set = workgroups of role r return at once
-#endif
-                                           // (0 commit, 1 integrate, 2 claim, 3 walk): what the launch costs without them
 };
 
 // Serialised pipelined launches (overflow list): the claim and walk workgroups of frame i+1 wait here until the commit phase
@@ -256,184 +271,6 @@ __device__ __forceinline__ bool wait_commit_done(int32_t *counters, int32_t tag,
     return reached != 0;
 }
 
-template <class In, class Depth, bool kBand, bool kSerial>
-__device__ __forceinline__ void frame_pipelined(const FrameParams &fpNew, const DevPtrs &dpNew, const In &inNew,
-                                                const FrameParams &fpOld, const DevPtrs &dpOld, const Depth &depthOld,
-                                                const PipeArgs &a)
-{
-    int32_t *counters = dpNew.counters;
-    // is frame i's commit phase inserting (live) or refusing everything?  Both numbers are stable while
-    // this launch runs: the count of claimed buckets was final when the previous launch ended, the
-    // free-block count was stored by its last commit workgroup (or, in a run's first launch, its first workgroup) in a word this
-    // launch does not write.
-    const int demandedOld = a.hasOld ? counters[kPipeCand + a.setOld] : 0;
-    const int candOld = min(demandedOld, (int)dpOld.candCapacity);
-    // With the overflow list an insertion in flight can change a chain link and a slot behind another bucket, which the
-    // claim phase cannot substitute from the claim words alone.  Those frames are serialised INSIDE the launch instead: the
-    // claim and walk workgroups of frame i+1 start when commit(i) has published its tag, and then read the table as it
-    // is -- one launch per frame still, TSDF update(i) still beside walk(i+1); commit(i) serves as many winners as the heap
-    // has blocks, like the unpipelined frame (no whole-frame refusal), and leaves its new entries for walk(i+1) to find.
-    // (kSerial = the context has the list on: a build of its own -- the code of this launch is weighed by the microsecond:
-    // the run-time form of this switch cost the C2 launch 0.7 us)
-    constexpr bool serial = kSerial;
-    const bool live = serial ? a.hasOld != 0u : a.hasOld && counters[kPipeHeapFree + a.setOld] >= counters[kPipeWinners + a.setOld];
-    // Roles by workgroup index: [commit][integrate][claim and walk interleaved as in
-    // frame_scan_claim_kernel]: frame i's deferred half runs first, at full width, then the table streams.
-    // In-process A/B on C2 / C3 (launch time, us): this order with 512 integrate workgroups 18.8 / 88.9; with
-    // 2048 of them (mostly idle, but dispatched before the first walk tile) 19.7 / 91.9; integrate and claim
-    // workgroups interleaved among the walk tiles 20.5 / 93.7 (the latency-bound block updates then hold the
-    // slots the stream needs); all claim tiles before the walk 20.4 / 93.0; the deferred half at the END of
-    // the grid, where the walk drains (or commit first, integrate last) 21.5 / 105.9 against 21.0 / 94.6 for
-    // this order on that box.  (Those orders were selectable at run time for a while; the run-time mapping
-    // with its 64-bit divisions per workgroup cost every launch 2 us and is gone.)
-    // EVERY figure above predates the alternating sweep (vh_walk.hip: walk_tile): the first walk ordinals of a launch were
-    // not served from an XCD's L2 then, so it did not matter in that way what was dealt among them.  With the sweep, the
-    // role table (profiles/pipelined_roles_reverse_C2.txt) has the reversal win 2.6 us for the walk alone and 1.5 us for the
-    // whole launch; the claim role and the deferred half each take about half a microsecond of it back.  Hence the claim
-    // window's lead (grouped_role: claimLead); the order of the roles is as it was.
-    const uint32_t b = blockIdx.x;
-    uint32_t role, index;                          // 0 commit, 1 integrate, 2 claim, 3 walk
-    if (b < a.commitBlocks) { role = 0; index = b; }
-    else if (a.walkIndexed) {
-        // The walk-free frame streams nothing: every role is a chain of dependent reads plus arithmetic, and a chain that starts
-        // late is the launch's tail.  The index walk's workgroups are few and their chain is the longest (bitmap -> buckets ->
-        // frustum test -> list), so they come first, then the TSDF update, then the claim tiles; spread among the claim tiles
-        // like the streaming walk they cost C2 10.8-11.2 us against 9.0-9.2, C3 28.1 against 27.6 (same box, generic build,
-        // profiles/r05_index_walk_shapes.txt); their issue priority makes no difference.
-        const uint32_t r = b - a.commitBlocks;
-        if (r < a.walkBlocks) { role = 3; index = r; }
-        else if (r < a.walkBlocks + a.integrateBlocks) { role = 1; index = r - a.walkBlocks; }
-        else { role = 2; index = r - a.walkBlocks - a.integrateBlocks; }
-    }
-    else if (b < a.commitBlocks + a.integrateBlocks) { role = 1; index = b - a.commitBlocks; }
-    else {
-        // the claim tiles are spread, in groups of 8, over the first a.claimSpan groups of the claim + walk workgroups
-        // (grouped_role: multiply-high by a.claimRatio = ceil(claimGroups * 2^32 / claimSpan), no division in the kernel;
-        // the host keeps a.commitBlocks + a.integrateBlocks a multiple of 8, so a walk ordinal = blockIdx mod 8)
-        const bool claims = grouped_role(b - a.commitBlocks - a.integrateBlocks, a.claimBlocks, a.claimSpan, a.claimRatio, a.claimLead, index);
-        role = claims ? 2u : 3u;
-        if (claims && index >= a.claimBlocks) return;          // (fills up the last claim group)
-    }
-#ifdef VH_DEBUG_SKIP_ROLES
-    if (a.skipRoles & (1u << role)) {
-        // (the commit role also clears the rotating counter sets: left uncleared, the lists a later mask's TSDF update reads grow
-        // over entries nobody wrote)
-        if (role == 0u && b == 0u && threadIdx.x == 0 && a.hasOld) {
-            clear_pipe_set(counters, a.setClear);
-            if (!a.hasNew) clear_pipe_set(counters, a.setNew);
-        }
-        return;
-    }
-#endif
-    // first launch of a run (no frame in flight): nobody pops the heap during it, so its first workgroup
-    // leaves the free-block count the NEXT launch will test frame i+1's insertions against
-    if (!a.hasOld && b == 0u && threadIdx.x == 0) counters[kPipeHeapFree + a.setNew] = counters[kHeapCounter] + 1;
-    if (role >= 2u) {
-        // ---- frame i+1: claim || walk ----
-        if (!a.hasNew) return;
-        if (serial && a.hasOld) {
-            // (the commit and integrate workgroups have the lowest indices of the grid: they are running or done when this one starts)
-            if (!wait_commit_done(counters, a.doneTag, a.spinLimit)) return;
-        }
-        const Pending pend{a.hasOld && !serial ? dpOld.claim : nullptr, dpOld.candidates, fpOld.epoch, live,
-                           serial ? -1 : kPipeWinners + a.setNew,
-                           a.filter && a.hasOld && !serial ? a.filter + a.filtOld : nullptr,
-                           a.filter && !serial ? a.filter + a.filtNew : nullptr};
-        if (role == 2u) {
-            __builtin_amdgcn_s_setprio(3);
-#ifdef VH_DEBUG_SKIP_ROLES
-            if (a.skipRoles & 16u) {           // diagnostics: the claim tiles end before their probes (what the probes' wait costs the launch)
-                FrameParams fpN = fpNew;
-                fpN.flags |= kFlagDebugNoProbe;
-                if (!kBand && a.claimPerWave) {
-                    const uint32_t tile = index * (256u / kWave) + threadIdx.x / kWave;
-                    if (tile < num_tiles(fpN)) claim_tile_wave<In>(fpN, dpNew, inNew, tile, kPipeCand + a.setNew, pend, a.planeNew, a.rawNew);
-                } else {
-                    claim_tile<In, kBand>(fpN, dpNew, inNew, index, kPipeCand + a.setNew, pend, a.planeNew, a.rawNew, a.walkIndexed != 0u);
-                }
-                return;
-            }
-#endif
-            if (!kBand && a.claimPerWave) {
-                // (a launch tile per wave: the host sized the role at a quarter of the tiles, vh_api_frame.hip)
-                const uint32_t tile = index * (256u / kWave) + threadIdx.x / kWave;
-                if (tile < num_tiles(fpNew)) claim_tile_wave<In>(fpNew, dpNew, inNew, tile, kPipeCand + a.setNew, pend, a.planeNew, a.rawNew);
-            } else {
-                claim_tile<In, kBand>(fpNew, dpNew, inNew, index, kPipeCand + a.setNew, pend, a.planeNew, a.rawNew, a.walkIndexed != 0u);
-            }
-        } else if (a.walkIndexed) {
-            flatten_index_tile(fpNew, dpNew, index, CompactOut{kPipeScan + a.setNew, kPipeScanB + a.setNew, a.numEntries},
-                               pend);                                              // (opt-in: not the reference's walk)
-        } else {
-            flatten_tile_ballot(fpNew, dpNew, a.numEntries, walk_tile(index, a.walkGroups, a.walkReverse),
-                                CompactOut{kPipeScan + a.setNew, kPipeScanB + a.setNew, a.numEntries}, pend);
-        }
-        return;
-    }
-    if (!a.hasOld) return;
-    // the filter frame i+2 will fill: cleared here (nobody reads or writes it during this launch); a flush launch clears
-    // the one a new frame would have filled as well, so that a run always starts on an empty one
-    if (role == 0u && a.filter) {
-        for (uint32_t t = index * 256u + threadIdx.x; t < kPendFilterWords; t += a.commitBlocks * 256u) {
-            a.filter[a.filtClear + t] = 0u;
-            if (!a.hasNew) a.filter[a.filtNew + t] = 0u;
-        }
-    }
-    const int scanOld = counters[kPipeScan + a.setOld];
-    if (role == 1u) {
-        // ---- frame i: TSDF update of the blocks its walk (and commit(i-1)) listed ----
-        integrate_list(fpOld, dpOld, dpOld.compact, scanOld, (int)index, (int)a.integrateBlocks, depthOld,
-                       counters[kPipeScanB + a.setOld], a.numEntries);
-        return;
-    }
-    // ---- frame i: commit ----
-    __shared__ VoxelEntry newEntry;
-    __shared__ int inserted;
-    const int workers = max(1, min(candOld, (int)a.commitBlocks));
-    if ((int)index >= workers) return;
-    for (int i = (int)index; i < candOld; i += (int)a.commitBlocks) {
-        if (threadIdx.x == 0) {
-            inserted = 0;
-            const int4 k = dpOld.candidates[i];
-            if (live) {
-                VoxelEntry e;
-                inserted = commit_candidate(fpOld, dpOld, k, e, (uint32_t)i, false) ? 1 : 0;
-                if (inserted) {
-                    newEntry = e;
-                    dpOld.compact[scanOld + atomicAdd(counters + kPipeNew + a.setOld, 1)] = e;
-                    // what walk(i+1) would have listed had it seen the entry
-                    if (a.hasNew && !serial && block_in_frustum(fpNew, e.pos[0], e.pos[1], e.pos[2]))
-                        dpNew.compact[atomicAdd(counters + kPipeScan + a.setNew, 1)] = e;
-                }
-            } else {
-                const uint32_t local = hash_block(k.x, k.y, k.z, fpOld.numBuckets) - fpOld.bucketLo;
-                const unsigned long long w = dpOld.claim[local];
-                if (claim_epoch(w) == fpOld.epoch && claim_slot(w) == (uint32_t)i) atomicAdd(counters + kHeapExhausted, 1);
-            }
-        }
-        __syncthreads();
-        if (inserted) integrate_block(fpOld, dpOld, newEntry, depthOld);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        __threadfence();
-        const int ticket = atomicAdd(counters + kCommitTicket, 1);
-        if (ticket == workers - 1) {
-            counters[kCompactCount] = scanOld + counters[kPipeScanB + a.setOld] + atomicAdd(counters + kPipeNew + a.setOld, 0);
-            counters[kLastCandidates] = demandedOld;
-            clear_pipe_set(counters, a.setClear);
-            if (!a.hasNew) clear_pipe_set(counters, a.setNew);      // flush launch: the set a new frame would have filled is unused: the next
-                                                                    // run starts on it (the host keeps rotating), and finds it empty
-            counters[kPipeHeapFree + a.setNew] = atomicAdd(counters + kHeapCounter, 0) + 1;   // what the next launch starts with
-            counters[kCommitTicket] = 0;
-            if (serial) {                          // every committer fenced before its ticket: the table is settled
-                __threadfence();
-                __hip_atomic_store(counters + kPipeCommitDone, a.doneTag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-}
-
 // The builds of the pipelined launch (kLean).  A lean build has both frames' option flags, the walk and the claim form folded in
 // when the kernel is BUILT; the host picks it when the context's state is exactly its lean_build() (vh_api_frame.hip: lean_for).
 enum : int {
@@ -454,6 +291,294 @@ constexpr LeanBuild lean_build(int kLean)
     return {kFlagWalkShort | (kLean % 2 == 0 ? kFlagWalkNt : 0u) | (kLean == kLeanRayDda || kLean == kLeanRayDdaNt ? kFlagBandRayDda : 0u),
             kLean >= kLeanIndexed, kLean >= kLeanIndexedWave};
 }
+
+// is frame i's commit phase inserting (live) or refusing everything?  Both numbers are stable while the launch runs: the
+// count of claimed buckets was final when the previous launch ended, the free-block count was stored by its last commit
+// workgroup (or, in a run's first launch, its first workgroup) in a word this launch does not write.  Asked by the roles that
+// need the answer, when they need it: commit per candidate pass, claim behind its vertex requests, walk only in a wave that
+// found an allocated entry.
+template <bool kSerial>
+__device__ __forceinline__ bool pending_live(uint32_t hasOld, const int32_t *counters, int32_t setOld)
+{
+    if (kSerial) return hasOld != 0u;
+    return hasOld && counters[kPipeHeapFree + setOld] >= counters[kPipeWinners + setOld];
+}
+
+// The launch's argument block behind its leading piece, one struct: the kernel's second and last parameter, so it lies in the
+// argument segment right behind the 64 bytes of the first, laid out as below.
+template <class In, class Depth>
+struct PipeKernargs {
+    FrameParams fpNew;
+    DevPtrs dpNew;
+    In inNew;
+    FrameParams fpOld;
+    DevPtrs dpOld;
+    Depth depthOld;
+    PipeArgs a;
+};
+// The kernel's parameter list as the argument segment lays it out: every parameter at the next offset that suits its
+// alignment, in order -- which is a struct of the parameters.  role_arguments reads the second one at the offset this gives;
+// launch_pipelined (vh_api_frame.hip) builds its two arguments as the members of one, so host and device agree by type.
+template <class In, class Depth>
+struct PipeSignature {
+    PipeLeadWords lead;
+    PipeKernargs<In, Depth> rest;
+};
+
+// The argument block as ONE ROLE reads it.  Read through the kernel's parameter, a field that two roles use is loaded once,
+// ahead of both -- the compiler places such a load in the block that dominates its uses, which is the role decision: that is
+// how the block of loads, waits and spills in front of every role came about, and it comes back with any field that the
+// claim role, a listing walk wave and the commit role share (the frustum of the new frame, the counters pointer ...).  So
+// each role takes the segment's address through an empty volatile asm at the point where it may start to read it: loads
+// behind that point cannot move ahead of it and are not merged with another role's.  (Scalar loads all the same: the asm
+// hands back a uniform pointer into the constant address space.)
+template <class In, class Depth, int kLean>
+__device__ __forceinline__ const PipeKernargs<In, Depth> &role_arguments()
+{
+    typedef PipeKernargs<In, Depth> K;
+    typedef PipeSignature<In, Depth> Signature;
+    static_assert(offsetof(Signature, lead) == 0 && offsetof(Signature, rest) == sizeof(PipeLeadWords),
+                  "frame_pipelined_kernel(lead, rest): rest lies right behind lead");
+    typedef const __attribute__((address_space(4))) char *SegmentBytes;
+    typedef const __attribute__((address_space(4))) K *SegmentPtr;
+    SegmentPtr p = (SegmentPtr)((SegmentBytes)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(Signature, rest));
+    asm volatile("" : "+s"(p));
+    const K &k = *(const K *)p;
+    // How a lean build's flags reach the device functions: as a fact about the arguments, not as a patched copy of them.
+    // The host launches build kLean only when both frames' flags ARE lean_build(kLean).flags (vh_api_frame.hip: lean_for),
+    // and this tells the compiler so: every `fp.flags & ...` down the call tree folds as it did when the kernel overwrote the
+    // word in by-value copies -- which made both structs live across every role.
+    constexpr uint32_t leanFlags = lean_build(kLean).flags;
+    if (kLean != kLeanNone) {
+        __builtin_assume(k.fpNew.flags == leanFlags);
+        __builtin_assume(k.fpOld.flags == leanFlags);
+    }
+    return k;
+}
+
+// l: the leading piece of the arguments, in registers; everything else is still in the argument block and is read by the
+// role that uses it (role_arguments).
+template <class In, class Depth, bool kBand, bool kSerial, int kLean>
+__device__ __forceinline__ void frame_pipelined(const PipeLead &l)
+{
+    typedef PipeKernargs<In, Depth> K;
+    constexpr LeanBuild lean = lean_build(kLean);
+    const bool walkIndexed = kLean != kLeanNone ? lean.indexed : l.walkIndexed != 0u;
+    // With the overflow list an insertion in flight can change a chain link and a slot behind another bucket, which the
+    // claim phase cannot substitute from the claim words alone.  Those frames are serialised INSIDE the launch instead: the
+    // claim and walk workgroups of frame i+1 start when commit(i) has published its tag, and then read the table as it
+    // is -- one launch per frame still, TSDF update(i) still beside walk(i+1); commit(i) serves as many winners as the heap
+    // has blocks, like the unpipelined frame (no whole-frame refusal), and leaves its new entries for walk(i+1) to find.
+    // (kSerial = the context has the list on: a build of its own -- the code of this launch is weighed by the microsecond:
+    // the run-time form of this switch cost the C2 launch 0.7 us)
+    constexpr bool serial = kSerial;
+    // Roles by workgroup index: [commit][integrate][claim and walk interleaved as in
+    // frame_scan_claim_kernel]: frame i's deferred half runs first, at full width, then the table streams.
+    // In-process A/B on C2 / C3 (launch time, us): this order with 512 integrate workgroups 18.8 / 88.9; with
+    // 2048 of them (mostly idle, but dispatched before the first walk tile) 19.7 / 91.9; integrate and claim
+    // workgroups interleaved among the walk tiles 20.5 / 93.7 (the latency-bound block updates then hold the
+    // slots the stream needs); all claim tiles before the walk 20.4 / 93.0; the deferred half at the END of
+    // the grid, where the walk drains (or commit first, integrate last) 21.5 / 105.9 against 21.0 / 94.6 for
+    // this order on that box.  (Those orders were selectable at run time for a while; the run-time mapping
+    // with its 64-bit divisions per workgroup cost every launch 2 us and is gone.)
+    // EVERY figure above predates the alternating sweep (vh_walk.hip: walk_tile): the first walk ordinals of a launch were
+    // not served from an XCD's L2 then, so it did not matter in that way what was dealt among them.  With the sweep, the
+    // role table (profiles/pipelined_roles_reverse_C2.txt) has the reversal win 2.6 us for the walk alone and 1.5 us for the
+    // whole launch; the claim role and the deferred half each take about half a microsecond of it back.  Hence the claim
+    // window's lead (grouped_role: claimLead); the order of the roles is as it was.
+    const uint32_t b = blockIdx.x;
+    uint32_t role, index;                          // 0 commit, 1 integrate, 2 claim, 3 walk
+    if (b < l.commitBlocks) { role = 0; index = b; }
+    else if (walkIndexed) {
+        // The walk-free frame streams nothing: every role is a chain of dependent reads plus arithmetic, and a chain that starts
+        // late is the launch's tail.  The index walk's workgroups are few and their chain is the longest (bitmap -> buckets ->
+        // frustum test -> list), so they come first, then the TSDF update, then the claim tiles; spread among the claim tiles
+        // like the streaming walk they cost C2 10.8-11.2 us against 9.0-9.2, C3 28.1 against 27.6 (same box, generic build,
+        // profiles/r05_index_walk_shapes.txt); their issue priority makes no difference.
+        const uint32_t r = b - l.commitBlocks;
+        if (r < l.walkBlocks) { role = 3; index = r; }
+        else if (r < l.walkBlocks + l.integrateBlocks) { role = 1; index = r - l.walkBlocks; }
+        else { role = 2; index = r - l.walkBlocks - l.integrateBlocks; }
+    }
+    else if (b < l.commitBlocks + l.integrateBlocks) { role = 1; index = b - l.commitBlocks; }
+    else {
+        // the claim tiles are spread, in groups of 8, over the first l.claimSpan groups of the claim + walk workgroups
+        // (grouped_role: multiply-high by l.claimRatio = ceil(claimGroups * 2^32 / claimSpan), no division in the kernel;
+        // the host keeps l.commitBlocks + l.integrateBlocks a multiple of 8, so a walk ordinal = blockIdx mod 8)
+        const bool claims = grouped_role(b - l.commitBlocks - l.integrateBlocks, l.claimBlocks, l.claimSpan, l.claimRatio, l.claimLead, index);
+        role = claims ? 2u : 3u;
+        if (claims && index >= l.claimBlocks) return;          // (fills up the last claim group)
+    }
+#ifdef VH_DEBUG_SKIP_ROLES
+    if (l.skipRoles & (1u << role)) {
+        // (the commit role also clears the rotating counter sets: left uncleared, the lists a later mask's TSDF update reads grow
+        // over entries nobody wrote)
+        const K &k = role_arguments<In, Depth, kLean>();
+        if (role == 0u && b == 0u && threadIdx.x == 0 && l.hasOld) {
+            clear_pipe_set(k.dpNew.counters, k.a.setClear);
+            if (!l.hasNew) clear_pipe_set(k.dpNew.counters, k.a.setNew);
+        }
+        // (... and in a run's first launch the workgroup of claim tile 0 leaves the free-block count, below, skipped or not)
+        if (!l.hasOld && role == 2u && index == 0u && threadIdx.x == 0)
+            k.dpNew.counters[kPipeHeapFree + k.a.setNew] = k.dpNew.counters[kHeapCounter] + 1;
+        return;
+    }
+    // (mask 16, the claim tiles end before their probes: the host sets kFlagDebugNoProbe in the context's flags, which selects
+    // the generic build, and claim_tile reads it there)
+#endif
+    if (role >= 2u) {
+        // ---- frame i+1: claim || walk ----
+        if (!l.hasNew) return;
+        if (serial && l.hasOld) {
+            // (the commit and integrate workgroups have the lowest indices of the grid: they are running or done when this one starts)
+            const K &k = role_arguments<In, Depth, kLean>();
+            if (!wait_commit_done(k.dpNew.counters, k.a.doneTag, k.a.spinLimit)) return;
+        }
+        // the frame whose commit phase runs beside this workgroup: `live` is two words of device memory, the rest comes from
+        // the far end of the arguments -- made behind a tile's own first loads
+        const auto pending = [&](const K &k) {
+            return Pending{l.hasOld && !serial ? k.dpOld.claim : nullptr, k.dpOld.candidates, k.fpOld.epoch,
+                           pending_live<serial>(l.hasOld, k.dpNew.counters, k.a.setOld),
+                           serial ? -1 : kPipeWinners + k.a.setNew,
+                           k.a.filter && l.hasOld && !serial ? k.a.filter + k.a.filtOld : nullptr,
+                           k.a.filter && !serial ? k.a.filter + k.a.filtNew : nullptr};
+        };
+        if (role == 3u && !walkIndexed) {
+            // The reference's walk: tile and loads from the leading piece alone -- no wait, no spill and no other read between
+            // the role decision and the last ptr load (a lean build; the generic one reads the flags word first).  A wave
+            // that finds all its entries free -- nearly every wave -- ends there; only one that has something to list goes
+            // on to read the arguments: frustum, list and counters, the pending frame.
+            const uint32_t flags = kLean != kLeanNone ? lean.flags : role_arguments<In, Depth, kLean>().fpNew.flags;
+            const uint32_t tile = walk_tile(index, l.walkGroups, l.walkReverse);
+            // (the pointer arrived as two words of the leading vector: named a pointer to device memory here, or the loads
+            // would be flat ones)
+            typedef const __attribute__((address_space(1))) VoxelEntry *GlobalTable;
+            // (walk_load_tile asks a FrameParams for the non-temporal flag and a DevPtrs for the table: two locals that hold
+            // just those, the rest of them is never read)
+            FrameParams loadFp{};
+            DevPtrs loadDp{};
+            loadFp.flags = flags;
+            loadDp.table = (VoxelEntry *)(GlobalTable)(uintptr_t)l.table;
+            const auto walk = [&](auto &ptrs) {
+                walk_load_tile(loadFp, loadDp, l.numEntries, tile, ptrs);
+                if (!walk_wave_live(ptrs)) return;
+                const K &k = role_arguments<In, Depth, kLean>();
+                walk_process_tile(k.fpNew, k.dpNew, tile, ptrs, CompactOut{kPipeScan + k.a.setNew, kPipeScanB + k.a.setNew, l.numEntries},
+                                  pending(k));
+            };
+            if (flags & kFlagWalkShort) {
+                int32_t ptrs[kEntriesPerLaneShort];
+                walk(ptrs);
+            } else {
+                int32_t ptrs[kEntriesPerLane];
+                walk(ptrs);
+            }
+            return;
+        }
+        const K &k = role_arguments<In, Depth, kLean>();
+        if (role == 3u) {
+            flatten_index_tile(k.fpNew, k.dpNew, index, CompactOut{kPipeScan + k.a.setNew, kPipeScanB + k.a.setNew, l.numEntries},
+                               pending(k));                                        // (opt-in: not the reference's walk)
+            return;
+        }
+        __builtin_amdgcn_s_setprio(3);
+        // first launch of a run (no frame in flight): nobody pops the heap during it, so one of its workgroups -- the one of claim
+        // tile 0: a claim tile has the time, a walk workgroup does not -- leaves the free-block count the NEXT launch will test
+        // frame i+1's insertions against
+        const auto leave_heap_free = [&]() {
+            if (!l.hasOld && index == 0u && threadIdx.x == 0) k.dpNew.counters[kPipeHeapFree + k.a.setNew] = k.dpNew.counters[kHeapCounter] + 1;
+        };
+        if (!kBand && lean.claimPerWave) {
+            // (a launch tile per wave: the host sized the role at a quarter of the tiles, vh_api_frame.hip)
+            leave_heap_free();
+            const uint32_t tile = index * (256u / kWave) + threadIdx.x / kWave;
+            if (tile < num_tiles(k.fpNew))
+                claim_tile_wave<In>(k.fpNew, k.dpNew, k.inNew, tile, kPipeCand + k.a.setNew, pending(k), k.a.planeNew, k.a.rawNew);
+        } else {
+            // the tile's pixels are requested first; what the probes need is read while they are in flight
+            // (load_pixel here, with the private depth copy; claim_tile then takes the pixel from the register: LoadedPixel)
+            const PixelVertex p = load_pixel(k.fpNew, k.inNew, index, threadIdx.x, k.a.planeNew, k.a.rawNew);
+            leave_heap_free();
+            claim_tile<LoadedPixel, kBand>(k.fpNew, k.dpNew, LoadedPixel{p.v, p.n}, index, kPipeCand + k.a.setNew, pending(k), nullptr, nullptr,
+                                           walkIndexed);
+        }
+        return;
+    }
+    if (!l.hasOld) return;
+    const K &k = role_arguments<In, Depth, kLean>();
+    const FrameParams &fpNew = k.fpNew, &fpOld = k.fpOld;
+    const DevPtrs &dpNew = k.dpNew, &dpOld = k.dpOld;
+    const Depth &depthOld = k.depthOld;
+    const PipeArgs &a = k.a;
+    int32_t *counters = dpNew.counters;
+    if (role == 1u) {
+        // ---- frame i: TSDF update of the blocks its walk (and commit(i-1)) listed ----
+        // (the two ends' counts are the role's first reads: its chain is counts -> entry -> voxels)
+        const int scanOld = counters[kPipeScan + a.setOld], scanOldB = counters[kPipeScanB + a.setOld];
+        integrate_list(fpOld, dpOld, dpOld.compact, scanOld, (int)index, (int)l.integrateBlocks, depthOld, scanOldB, l.numEntries);
+        return;
+    }
+    // ---- frame i: commit ----
+    // (its chain -- counts -> candidate -> bucket -> heap -> block -- starts before the filter's stores are issued)
+    const int demandedOld = counters[kPipeCand + a.setOld];
+    const int scanOld = counters[kPipeScan + a.setOld];
+    const bool live = pending_live<serial>(l.hasOld, counters, a.setOld);
+    const int candOld = min(demandedOld, (int)dpOld.candCapacity);
+    // the filter frame i+2 will fill: cleared here (nobody reads or writes it during this launch); a flush launch clears
+    // the one a new frame would have filled as well, so that a run always starts on an empty one
+    if (a.filter) {
+        for (uint32_t t = index * 256u + threadIdx.x; t < kPendFilterWords; t += l.commitBlocks * 256u) {
+            a.filter[a.filtClear + t] = 0u;
+            if (!l.hasNew) a.filter[a.filtNew + t] = 0u;
+        }
+    }
+    __shared__ VoxelEntry newEntry;
+    __shared__ int inserted;
+    const int workers = max(1, min(candOld, (int)l.commitBlocks));
+    if ((int)index >= workers) return;
+    for (int i = (int)index; i < candOld; i += (int)l.commitBlocks) {
+        if (threadIdx.x == 0) {
+            inserted = 0;
+            const int4 k = dpOld.candidates[i];
+            if (live) {
+                VoxelEntry e;
+                inserted = commit_candidate(fpOld, dpOld, k, e, (uint32_t)i, false) ? 1 : 0;
+                if (inserted) {
+                    newEntry = e;
+                    dpOld.compact[scanOld + atomicAdd(counters + kPipeNew + a.setOld, 1)] = e;
+                    // what walk(i+1) would have listed had it seen the entry
+                    if (l.hasNew && !serial && block_in_frustum(fpNew, e.pos[0], e.pos[1], e.pos[2]))
+                        dpNew.compact[atomicAdd(counters + kPipeScan + a.setNew, 1)] = e;
+                }
+            } else {
+                const uint32_t local = hash_block(k.x, k.y, k.z, fpOld.numBuckets) - fpOld.bucketLo;
+                const unsigned long long w = dpOld.claim[local];
+                if (claim_epoch(w) == fpOld.epoch && claim_slot(w) == (uint32_t)i) atomicAdd(counters + kHeapExhausted, 1);
+            }
+        }
+        __syncthreads();
+        if (inserted) integrate_block(fpOld, dpOld, newEntry, depthOld);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const int ticket = atomicAdd(counters + kCommitTicket, 1);
+        if (ticket == workers - 1) {
+            counters[kCompactCount] = scanOld + counters[kPipeScanB + a.setOld] + atomicAdd(counters + kPipeNew + a.setOld, 0);
+            counters[kLastCandidates] = demandedOld;
+            clear_pipe_set(counters, a.setClear);
+            if (!l.hasNew) clear_pipe_set(counters, a.setNew);      // flush launch: the set a new frame would have filled is unused: the next
+                                                                    // run starts on it (the host keeps rotating), and finds it empty
+            counters[kPipeHeapFree + a.setNew] = atomicAdd(counters + kHeapCounter, 0) + 1;   // what the next launch starts with
+            counters[kCommitTicket] = 0;
+            if (serial) {                          // every committer fenced before its ticket: the table is settled
+                __threadfence();
+                __hip_atomic_store(counters + kPipeCommitDone, a.doneTag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
 // kBand: the new frame allocates a truncation band (vh_set_alloc_band > 0); false = the reference's frame, without the band code
 // kLean != kLeanNone: everything the flags guard (overflow list, DDA band, TSDF-update variants, the other walk forms) is
 // folded away by the compiler: 3.3 k instead of 6.8 k instructions; same box, same process: C2 18.35 -> 17.57 us, C3 69.4 ->
@@ -463,19 +588,18 @@ constexpr LeanBuild lean_build(int kLean)
 // (Eight waves per SIMD instead of the seven the 106 SGPRs allow -- __launch_bounds__(256, 8): 78 SGPRs, 129 instead of 100 of
 // them spilled to VGPR lanes -- measured in round 4, same box: C2 17.69 -> 18.37 us, C3 69.0 -> 69.4, C2 with the band 22.9 ->
 // 25.4.  The launch does not lack wave slots; the spill traffic lengthens the claim tiles.  profiles/r04_ab_pipe_waves.txt)
+// (the kernel itself reads its first parameter, the leading piece, and nothing of the second: role_arguments)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpsabi"
 template <class In, class Depth, bool kBand, bool kSerial, int kLean>
-__global__ __launch_bounds__(256) void frame_pipelined_kernel(FrameParams fpNew, const DevPtrs dpNew, const In inNew,
-                                                              FrameParams fpOld, const DevPtrs dpOld,
-                                                              const Depth depthOld, PipeArgs a)
+__global__ __launch_bounds__(256) void frame_pipelined_kernel(const PipeLeadWords lead, const PipeKernargs<In, Depth>)
 {
-    constexpr LeanBuild lean = lean_build(kLean);
-    if (kLean != kLeanNone) {
-        fpNew.flags = lean.flags;
-        fpOld.flags = lean.flags;
-        a.walkIndexed = lean.indexed ? 1u : 0u;
-    }
-    a.claimPerWave = lean.claimPerWave ? 1u : 0u;
-    frame_pipelined<In, Depth, kBand, kSerial>(fpNew, dpNew, inNew, fpOld, dpOld, depthOld, a);
+    // (the parameters are PipeSignature's members, in its order: role_arguments finds the second through that struct)
+    static_assert(std::is_same<decltype(PipeSignature<In, Depth>::lead), PipeLeadWords>::value &&
+                  std::is_same<decltype(PipeSignature<In, Depth>::rest), PipeKernargs<In, Depth>>::value, "keep PipeSignature in step");
+    const PipeLead l = __builtin_bit_cast(PipeLead, lead);
+    frame_pipelined<In, Depth, kBand, kSerial, kLean>(l);
 }
+#pragma clang diagnostic pop
 
 }  // namespace vh

@@ -159,6 +159,16 @@ __device__ __forceinline__ void walk_process_tile(const FrameParams &fp, const D
         compact_append(dp, out, tileIndex, mask, hit, ent);
     }
 }
+// walk_process_tile's first question on its own: does the wave hold an allocated entry at all?  Nearly every wave does not.
+// The pipelined launch asks it before it reads anything that only a listing wave needs (vh_frame.hip: the walk role).
+template <int kN>
+__device__ __forceinline__ bool walk_wave_live(const int32_t (&ptrs)[kN])
+{
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < kN; ++j) any |= (ptrs[j] != VH_FREE_BLOCK);
+    return __ballot(any) != 0ull;
+}
 
 // Entries per lane of the frame's walk: 4 (kFlagWalkShort, set at creation).
 // Twice the workgroups with half the loads each stream faster than 8 per lane once a workgroup costs
