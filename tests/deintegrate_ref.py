@@ -2,7 +2,8 @@
 multiply and add rounded on its own, in the order the header writes them.
 
 apply_frame(..., sign=+1) is the TSDF update of integrateDepthMap restated (tests/test_deintegrate_ref_cpu.py pins it to the
-oracle bit for bit); sign=-1 takes the same frame's samples out again.  visible_entries() is the block set: the allocated
+oracle bit for bit on the golden scenes, tests/test_tsdf_cases_cpu.py on crafted depth and stored voxels, non-finite ones
+included); sign=-1 takes the same frame's samples out again.  visible_entries() is the block set: the allocated
 entries that pass blockInFrustum, in table order -- vh_set_pose + vh_flatten.
 """
 import numpy as np
@@ -123,7 +124,7 @@ def apply_frame(voxels, entries, params, semantics, proj, pose_inv, pose, depth_
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         if sign > 0:
             nsdf = ((os_ * ow) + (s * cw)) / (ow + cw)
-            nw = np.minimum(F(params.integrationWeightMax), ow + cw)
+            nw = np.fmin(F(params.integrationWeightMax), ow + cw)         # fminf: a stored NaN weight becomes the cap
             change = ok
             stats = dict(untouched=int((~ok).sum()), reset=0, partial=0, updated=int(ok.sum()))
         else:
