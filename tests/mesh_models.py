@@ -420,13 +420,14 @@ def key_for_bucket(x, y, bucket, num_buckets):
 
 
 SLICE_BUCKETS = 1 << 21        # 2048 slices of 1024 buckets: two tiles of the slice scan
+SLICE_BALL_LO = (94, 31, -56)  # many_slices: the ball's 12^3 blocks begin here (away from the origin, where the hash crowds)
 
 
 def many_slices(seed=23):
     """A ball of 12^3 blocks plus 1500 lone blocks with a plane through them, in a table of 2^21 buckets: entries in both
     tiles of the slice scan, in the last slice and in the last bucket."""
     rng = np.random.RandomState(seed)
-    lo = np.array((94, 31, -56))                                               # (away from the origin, where the hash crowds)
+    lo = np.array(SLICE_BALL_LO)
     model = as_model(*ball_model(cube_keys(lo, lo + 12), lo * 8 + 48.3, 40.3, seed + 1))
     taken = set()
     lone = []
@@ -444,6 +445,18 @@ def many_slices(seed=23):
     for k in lone:
         model[k] = plane_block(rng)
     return model
+
+
+def many_slices_table(vh, tmp_path):
+    """many_slices() loaded into its table of 2^21 buckets of 2 slots."""
+    gt = vh.SDFHashtable(vh.default_params(numBuckets=SLICE_BUCKETS, bucketSize=2, numVoxelBlocks=4096), 640, 480, 1)
+    return load_model(gt, many_slices(), tmp_path)
+
+
+def in_both_slice_tiles(entries):
+    """Whether entry indices of that table lie in both tiles of the slice scan: on both sides of bucket 2^20."""
+    bucket = np.asarray(entries) // 2
+    return bool((bucket < SLICE_BUCKETS // 2).any() and (bucket >= SLICE_BUCKETS // 2).any())
 
 
 TILE_BUCKETS, TILE_BUCKET_SIZE = 1 << 19, 8

@@ -288,6 +288,28 @@ def test_many_blocks(vh, torch_cuda, tmp_path):
     gt.close()
 
 
+def test_more_than_one_tile_of_slices(vh, torch_cuda, tmp_path):
+    """The list walk over 2 048 slices, two tiles of the slice scan: a box that cuts the ball of mesh_models.many_slices, and
+    no region."""
+    gt = mm.many_slices_table(vh, tmp_path)
+    table = gt.hash_table()
+    model, order = mm.model_of(table, gt.sdf_blocks()), cr.order_of(table)
+    live = np.nonzero(table["ptr"] != -1)[0]
+    lo = np.array(mm.SLICE_BALL_LO)
+    box = (tuple(int(v) for v in lo + (4, 0, 2)), tuple(int(v) for v in lo + (9, 12, 40)))
+    for region in (box, None):
+        want = same_as_reference(gt, model, order, cr.INSIDE, 14, region)
+        listed = live[[k in want.rank for k in order]]
+        print(f"region {region}: {want.stats}")
+        assert len(listed) == want.stats["blocks"] and mm.in_both_slice_tiles(listed) and want.stats["components"] >= 1
+        if region is None:
+            assert len(listed) == len(live) and (listed // 2 == mm.SLICE_BUCKETS - 1).sum() == 2
+            assert want.stats["components"] > 1500                    # (the lone blocks: a piece each)
+        else:
+            assert 500 < len(listed) < 12 ** 3 and mm.in_both_slice_tiles(np.setdiff1d(live, listed))
+    gt.close()
+
+
 # ---- 6. removal ------------------------------------------------------------------------------------------------------
 def heap_is_sound(gt):
     c, table = gt.counters(), gt.hash_table()

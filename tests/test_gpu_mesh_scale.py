@@ -1,6 +1,6 @@
 """vh_extract_mesh at the sizes that reach the paths a small room never does: workgroups of mesh_block_kernel that run
 several passes (more than 8 192 listed blocks), more than one tile of slice counts (more than 2^20 buckets), more than 256
-tiles of block counts (the carry of mesh_scan_totals_kernel from one round to the next), and a view context whose record
+tiles of block counts (the carry of block_scan_totals_kernel from one round to the next), and a view context whose record
 count grows and shrinks between extractions.  Models: tests/mesh_models.py; comparison: same_as_reference of
 tests/test_gpu_mesh.py (bit for bit, in order).  tests/test_mesh_models_cpu.py checks the models' conditions without a GPU."""
 import numpy as np
@@ -12,7 +12,7 @@ from test_gpu_mesh import same_as_reference
 
 pytestmark = pytest.mark.gpu
 U = np.uint32
-GRID, TILE, SLICE = 8192, 1024, 1024          # mesh_block_kernel's grid limit, kMeshScanTile, kMeshSliceBuckets
+GRID, TILE, SLICE = 8192, 1024, 1024          # mesh_block_kernel's grid limit, kScanTile, kListSliceBuckets
 
 
 def emitting_positions(table, info):

@@ -9,6 +9,7 @@ import pytest
 
 import deintegrate_cases as DC
 import merge_color_cases as CC
+import mesh_models as mm
 import stream_cases as SC
 import stream_ref as S
 from voxelhashing_demo_amd import streaming
@@ -462,4 +463,63 @@ def test_block_store_on_the_gpu(oracle, vh, torch_cuda, sem):
     st = store.restore_all(gt)
     assert st["placed"] == outside.sum() - ring.sum() and st["stored"] == 0
     S.same_models(CC.model(CC.snapshot(gt)), original)
+    gt.close()
+
+
+# ---- 11. more than one tile of slice counts --------------------------------------------------------------------------------------
+def selection_spans_the_table(table, order, last_bucket):
+    """The conditions that make a selection of many_slices' table mean something: selected entries in both tiles of the slice
+    scan, unselected allocated entries in both, and (last_bucket) both entries of the last bucket selected."""
+    live = np.nonzero(table["ptr"] != -1)[0]
+    assert mm.in_both_slice_tiles(order) and mm.in_both_slice_tiles(np.setdiff1d(live, order))
+    assert not last_bucket or (order // 2 == mm.SLICE_BUCKETS - 1).sum() == 2
+
+
+def records_of(chunk, table, vox, order, selected):
+    """`chunk` holds the blocks of entries `order` of the downloaded table, in that order, bit for bit."""
+    assert chunk["selected"] == selected and len(chunk["keys"]) == len(order) and chunk["colors"] is None
+    assert np.array_equal(chunk["keys"], table["pos"][order])
+    at = (table["ptr"][order].astype(np.int64)[:, None] + np.arange(512)[None, :]).reshape(-1)
+    assert np.array_equal(np.ascontiguousarray(chunk["voxels"]).view(U).reshape(-1), vox[at].view(U).reshape(-1))
+
+
+@pytest.mark.parametrize("kind", ["outside_sphere", "box"])
+def test_more_than_one_tile_of_slices(vh, torch_cuda, tmp_path, kind):
+    """The list walk of vh_stream_out over 2 048 slices, two tiles of the slice scan: the count-only call, a call with a
+    capacity below the selection and the full call, against the rule on the downloaded table."""
+    gt = mm.many_slices_table(vh, tmp_path)
+    vs = gt.params.voxelSize
+    lo = np.array(mm.SLICE_BALL_LO)
+    cube = set(mm.cube_keys(lo, lo + 12))
+    # the ball's block centres lie within 77.6 voxels of its centre; the box cuts it on x and z
+    region = {"outside_sphere": S.sphere((lo * 8 + 48.3) * vs, 80 * vs, invert=True),
+              "box": S.box(lo + (4, 0, 2), lo + (9, 12, 40))}[kind]
+    table, vox = gt.hash_table(), gt.sdf_blocks()
+    model = mm.model_of(table, vox)
+    order = S.selection_of_table(table, region, vs)
+    chosen = set(map(tuple, table["pos"][order].tolist()))
+    print(f"{kind}: {len(order)} of {len(model)} blocks selected, {len(chosen & cube)} of the ball's {len(cube)}")
+    selection_spans_the_table(table, order, last_bucket=kind == "outside_sphere")
+    if kind == "outside_sphere":
+        assert not chosen & cube                                                    # the radius covers the ball
+    else:
+        assert 0 < len(chosen & cube) < len(cube)                                   # the box cuts it
+
+    assert gt.stream_count(region) == len(order)                                   # the count-only call: nothing changes
+    assert np.array_equal(gt.hash_table(), table) and np.array_equal(gt.sdf_blocks().view(U), vox.view(U))
+
+    cap = len(order) // 3                                                           # a capacity below the selection
+    first = gt.stream_out(region, capacity=cap)
+    records_of(first, table, vox, order[:cap], len(order))
+    mid_table, mid_vox = gt.hash_table(), gt.sdf_blocks()
+    taken = set(map(tuple, first["keys"].tolist()))
+    S.same_models(mm.model_of(mid_table, mid_vox), {k: v for k, v in model.items() if k not in taken})
+
+    rest = S.selection_of_table(mid_table, region, vs)                              # the full call: what is left of the selection
+    assert len(rest) == len(order) - cap
+    selection_spans_the_table(mid_table, rest, last_bucket=kind == "outside_sphere")
+    second = gt.stream_out(region)
+    records_of(second, mid_table, mid_vox, rest, len(rest))
+    S.same_models(mm.model_of(gt.hash_table(), gt.sdf_blocks()), {k: v for k, v in model.items() if k not in chosen})
+    assert gt.stream_count(region) == 0
     gt.close()

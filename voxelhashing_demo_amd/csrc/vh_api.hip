@@ -249,10 +249,10 @@ struct vh_context {
     int blockParity = 0;                   // which counter word the next vh_render_blocks appends through
     const Voxel *viewBlocks = nullptr;     // import: the record buffer the view table's ptrs address
     int32_t viewCount = 0;                 // records of the last import (their buckets are listed in compactMask)
-    // vh_extract_mesh (vh_api_mesh.hip): scratch of the first call, kept
+    // the ordered block list (vh_api_blocklist.hip: BlockListScratch names the parts): scratch of the first call that lists, kept
     DevBuf<int4> meshItems;                // the listed blocks {x, y, z, ptr}, in entry order
-    DevBuf<uint32_t> meshCounts;           // per-slice entry counts, then per-block triangle counts (scanned in place)
-    DevBuf<unsigned long long> meshTotals; // the scans' tile totals, then {listed blocks, triangles}
+    DevBuf<uint32_t> meshCounts;           // per-slice entry counts, then the caller's per-block counts (scanned in place)
+    DevBuf<unsigned long long> meshTotals; // the scans' tile totals, then two result words: {listed blocks, the caller's total}
     int meshVariant = 0;                   // option "mesh_variant": 0 = 9^3 apron in LDS, 1 = corners straight from global memory
     // vh_extract_mesh_indexed: scratch of its first call, kept
     DevBuf<uint32_t> meshWords;            // per listed block 512 words {vertex prefix << 7 | edge mask}, then the per-block vertex counts, then listPos[ptr >> 9]
@@ -264,6 +264,15 @@ struct vh_context {
     StreamScratch streaming;               // vh_stream_in, vh_stream_*_host: scratch of the first call, kept
     ComponentScratch components;           // vh_components, vh_remove_components: scratch of the first call, kept
 };
+
+// a scratch buffer (a DevBuf the context keeps) of at least `count` elements; what still uses a smaller one is synchronised away first
+template <class T>
+static int reserve_scratch(vh_context *c, DevBuf<T> &buf, size_t count, const char *what)
+{
+    if (buf.size() >= count && buf.get()) return VH_OK;
+    VH_HIP(hipStreamSynchronize(c->stream));
+    return buf.alloc(count, what);
+}
 
 struct DeviceGuard {
     int prev = -1;
@@ -394,6 +403,7 @@ static int settle(vh_context *c);              // ... and folds a two-ended comp
 static int ensure_color(vh_context *c);        // vh_api_color.hip: the colour volume, allocated and zeroed if the context has none (all or nothing)
 static int release_color(vh_context *c);       // vh_api_color.hip: the colour words of the blocks a deletion freed, if there is a colour volume
 static hipError_t reset_color(vh_context *c);  // ... and the whole volume back to "no colour"
+static DevPtrs model_ptrs(const vh_context *c);    // vh_api_blocklist.hip: c->dp, with a view table's voxels where they live, in the records
 
 static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_context **out)
 {
@@ -627,6 +637,7 @@ static int ensure_band_candidates(vh_context *c)
 #include "vh_api_frame.hip"
 #include "vh_api_shard.hip"
 #include "vh_api_model.hip"
+#include "vh_api_blocklist.hip"
 #include "vh_api_mesh.hip"
 #include "vh_api_sample.hip"
 #include "vh_api_esdf.hip"

@@ -1,6 +1,6 @@
 // vh_api_components.hip -- C-ABI, connected pieces of the model: vh_components, vh_components_host, vh_remove_components
 // (kernels: vh_components.hip).  Included by vh_api.hip after everything else (same translation unit: shares fail(), VH_HIP,
-// DeviceGuard, launch(), settle(), mesh_reserve() and the mesh list and scans, sweep_and_release(), stream_reserve()).
+// DeviceGuard, launch(), settle(), the block list and its scans, sweep_and_release(), reserve_scratch()).
 // Both calls read their stats back: they synchronise the context's stream.
 
 // What a call labels and, optionally, writes.
@@ -55,16 +55,11 @@ static int components_run(vh_context *c, const ComponentsCall &call, vh_componen
     *stats = st;
     int rc = settle(c);                                 // the frames queued so far are part of the model
     if (rc != VH_OK) return rc;
-    MeshRegion rg;
+    const BlockBox rg = block_box(call.region);
     bool emptyRegion = false;
-    for (int a = 0; a < 3; ++a) {
-        rg.lo[a] = call.region ? call.region->block_lo[a] : INT32_MIN;
-        rg.hi[a] = call.region ? call.region->block_hi[a] : INT32_MAX;
-        emptyRegion = emptyRegion || rg.lo[a] >= rg.hi[a];
-    }
-    FrameParams fp = c->fp;
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);     // view table: voxels live in the records
+    for (int a = 0; a < 3; ++a) emptyRegion = emptyRegion || rg.lo[a] >= rg.hi[a];
+    const FrameParams fp = c->fp;
+    const DevPtrs dp = model_ptrs(c);
     hipStream_t s = c->stream;
     if (emptyRegion) {                                  // no block is listed: no component, every label of the box is NONE
         if (call.haveBox) {
@@ -75,44 +70,32 @@ static int components_run(vh_context *c, const ComponentsCall &call, vh_componen
         return VH_OK;
     }
 
-    // 1. the ordered block list: the mesh's count, scan and write (its scratch and its scans) with the region as predicate
-    const size_t slices = ((size_t)c->ownedBuckets + kMeshSliceBuckets - 1) / kMeshSliceBuckets;
-    const size_t blocks = std::max<size_t>(1, std::min<size_t>(c->numEntries, c->viewBlocks ? (size_t)c->viewCount : (size_t)c->params.numVoxelBlocks));
-    const size_t rankSize = c->viewBlocks ? (((size_t)c->viewCount * 514 + 2) >> 9) + 1 : (size_t)c->params.numVoxelBlocks;
-    if ((rc = mesh_reserve(c, slices, blocks)) != VH_OK) return rc;
-    const size_t listed = c->meshItems.size();
-    const size_t labelled = std::min<size_t>(listed, kCompMaxBlocks);       // (beyond the limit nothing is labelled)
+    // 1. the ordered block list with the region as predicate (its scratch first: it sizes this call's own)
+    BlockListScratch sc;
+    if ((rc = block_list_reserve(c, sc)) != VH_OK) return rc;
+    const size_t rankSize = ptr_map_size(c);
+    const uint32_t listCapacity = sc.listCapacity;
+    const size_t labelled = std::min<size_t>(listCapacity, kCompMaxBlocks);       // (beyond the limit nothing is labelled)
     ComponentScratch &cs = c->components;
-    if ((rc = stream_reserve(c, cs.parent, labelled * kBlockVoxels, "component parents")) != VH_OK) return rc;
-    if ((rc = stream_reserve(c, cs.rank, rankSize, "component block ranks")) != VH_OK) return rc;
-    if ((rc = stream_reserve(c, cs.rootBits, labelled * 8 + kCompWords, "component root bits")) != VH_OK) return rc;
-    if (call.remove && (rc = stream_reserve(c, cs.keys, labelled, "component key list")) != VH_OK) return rc;
-    const uint32_t listCapacity = (uint32_t)listed;
-    uint32_t *sliceCount = c->meshCounts, *rootCount = sliceCount + slices;
-    unsigned long long *sliceTiles = c->meshTotals;
-    unsigned long long *rootTiles = sliceTiles + (slices + kMeshScanTile - 1) / kMeshScanTile;
-    unsigned long long *result = rootTiles + (listed + kMeshScanTile - 1) / kMeshScanTile;          // {listed blocks, components}
+    if ((rc = reserve_scratch(c, cs.parent, labelled * kBlockVoxels, "component parents")) != VH_OK) return rc;
+    if ((rc = reserve_scratch(c, cs.rank, rankSize, "component block ranks")) != VH_OK) return rc;
+    if ((rc = reserve_scratch(c, cs.rootBits, labelled * 8 + kCompWords, "component root bits")) != VH_OK) return rc;
+    if (call.remove && (rc = reserve_scratch(c, cs.keys, labelled, "component key list")) != VH_OK) return rc;
+    uint32_t *rootCount = sc.blockCount;
+    unsigned long long *rootTiles = sc.blockTiles, *result = sc.result;             // {listed blocks, components}
     unsigned long long *rootBits = cs.rootBits, *words = rootBits + labelled * 8;
     uint32_t *parent = cs.parent, *rank = cs.rank;
-    const int4 *items = c->meshItems;
+    const int4 *items = sc.items;
     const unsigned long long *numItems = result;
 
     VH_HIP(hipMemsetAsync(rank, 0xFF, sizeof(uint32_t) * rankSize, s));     // no block is listed yet
     VH_HIP(hipMemsetAsync(words, 0, sizeof(unsigned long long) * kCompWords, s));
     VH_HIP(hipMemsetAsync(result, 0, sizeof(unsigned long long) * 2, s));
-    const unsigned listGrid = (unsigned)grid_for(slices, 4), sliceTileGrid = (unsigned)grid_for(slices, kMeshScanTile);
-    hipLaunchKernelGGL(mesh_list_kernel<false>, dim3(listGrid), dim3(256), 0, s, fp, dp, rg, c->ownedBuckets, (uint32_t)slices,
-                       sliceCount, (const unsigned long long *)sliceTiles, (int4 *)c->meshItems, listCapacity);
-    hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(sliceTileGrid), dim3(256), 0, s, sliceCount, (const unsigned long long *)nullptr,
-                       (uint32_t)slices, sliceTiles);
-    hipLaunchKernelGGL(mesh_scan_totals_kernel, dim3(1), dim3(256), 0, s, sliceTiles, (const unsigned long long *)nullptr,
-                       (uint32_t)slices, (unsigned long long)listCapacity, result);
-    hipLaunchKernelGGL(mesh_list_kernel<true>, dim3(listGrid), dim3(256), 0, s, fp, dp, rg, c->ownedBuckets, (uint32_t)slices,
-                       sliceCount, (const unsigned long long *)sliceTiles, (int4 *)c->meshItems, listCapacity);
+    if ((rc = list_blocks(c, fp, dp, rg, true, sc)) != VH_OK) return rc;
 
     // 2. the labelling.  ("components_launches" k = 1..6: a timing run stops behind stage k and returns no result)
     const int stages = c->componentsLaunches ? c->componentsLaunches : 7;
-    const unsigned blockGrid = (unsigned)std::min<size_t>(labelled, 8192), tileGrid = (unsigned)grid_for(listed, kMeshScanTile);
+    const unsigned blockGrid = (unsigned)std::min<size_t>(labelled, 8192);
     if (stages >= 2)
         hipLaunchKernelGGL(comp_local_kernel, dim3(blockGrid), dim3(256), 0, s, dp, items, numItems, listCapacity, (int)call.target,
                            (int)call.connectivity, parent, rank, (uint32_t)rankSize);
@@ -125,9 +108,8 @@ static int components_run(vh_context *c, const ComponentsCall &call, vh_componen
         hipLaunchKernelGGL(comp_count_kernel, dim3(blockGrid), dim3(256), 0, s, numItems, listCapacity, parent,
                            (const unsigned long long *)rootBits, words);
     if (stages >= 6) {
-        // 3. the roots in id order: the mesh's scan over the roots per block, then the records
-        hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(tileGrid), dim3(256), 0, s, rootCount, numItems, 0u, rootTiles);
-        hipLaunchKernelGGL(mesh_scan_totals_kernel, dim3(1), dim3(256), 0, s, rootTiles, numItems, 0u, ~0ull, result + 1);
+        // 3. the roots in id order: the scan over the roots per block, then the records
+        scan_counts(s, rootCount, numItems, listCapacity, rootTiles, ~0ull, result + 1);
         hipLaunchKernelGGL(comp_records_kernel, dim3(blockGrid), dim3(256), 0, s, items, numItems, listCapacity, (const uint32_t *)parent,
                            (const unsigned long long *)rootBits, (const uint32_t *)rootCount, (const unsigned long long *)rootTiles,
                            (unsigned long long)call.capacity, reinterpret_cast<CompRecord *>(call.records), words);

@@ -86,8 +86,7 @@ extern "C" int vh_esdf_lattice(vh_context *c, const int32_t lo[3], const int32_t
     DeviceGuard guard(c->device);
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }      // the frames queued so far are part of the model
     FrameParams fp = c->fp;
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);     // view table: voxels live in the records
+    DevPtrs dp = model_ptrs(c);
 
     uint8_t *at = static_cast<uint8_t *>(d_workspace);
     unsigned long long *planeIn = reinterpret_cast<unsigned long long *>(at);

@@ -705,8 +705,7 @@ static int raycast_impl(vh_context *c, const float pose[16], float t_min, float 
     FrameParams fp = c->fp;
     std::memcpy(fp.T, pose, sizeof fp.T);
     dim3 grid((fp.width + 15) / 16, (fp.height + 15) / 16);
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);     // view table: voxels live in the records
+    DevPtrs dp = model_ptrs(c);
     int rc;
     if (c->raycastMode == VH_RAYCAST_FIXED_STEP) {
         const float q = (t_max - t_min) / fp.voxelSize;

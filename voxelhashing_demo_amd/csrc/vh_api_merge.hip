@@ -121,8 +121,7 @@ static int merge_impl(vh_context *dst, vh_context *src, const float src_to_dst[1
     dst->compactArmed = false;
     dst->occupiedCounter = kCompactCount;
     dst->foldA = -1;
-    DevPtrs srcDp = src->dp;
-    if (src->viewBlocks) srcDp.blocks = const_cast<Voxel *>(src->viewBlocks);     // view table: voxels live in the records
+    DevPtrs srcDp = model_ptrs(src);
     const dim3 grid((unsigned)dst->integrateGrid);
     if (colored) {
         uint32_t *dstColor = dst->color.get();

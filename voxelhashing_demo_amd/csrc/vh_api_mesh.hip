@@ -1,43 +1,24 @@
 // vh_api_mesh.hip -- C-ABI, the way out of the volume: vh_extract_mesh, vh_extract_mesh_indexed (kernels: vh_mesh.hip).
-// Included by vh_api.hip (same translation unit: shares fail(), VH_HIP, DeviceGuard, flush_pending()).
+// Included by vh_api.hip behind vh_api_blocklist.hip (same translation unit: shares fail(), VH_HIP, DeviceGuard, flush_pending(),
+// the block list and its scans).
 
-// Scratch of the extraction, allocated at the first call and kept (grown when a view context imports more records): the block
-// list, the slice and block counts, the scans' tile totals and two result words.  All or nothing: a failed allocation leaves
-// the context as it was.
-static int mesh_reserve(vh_context *c, size_t slices, size_t blocks)
-{
-    const size_t counts = slices + blocks;
-    const size_t totals = (slices + kMeshScanTile - 1) / kMeshScanTile + (blocks + kMeshScanTile - 1) / kMeshScanTile + 2;
-    if (c->meshItems.size() >= blocks && c->meshCounts.size() >= counts && c->meshTotals.size() >= totals) return VH_OK;
-    VH_HIP(hipStreamSynchronize(c->stream));           // (before an older, smaller set is freed)
-    DevBuf<int4> items;
-    DevBuf<uint32_t> cnt;
-    DevBuf<unsigned long long> tot;
-    int rc;
-    if ((rc = items.alloc(blocks, "mesh block list")) || (rc = cnt.alloc(counts, "mesh counts")) ||
-        (rc = tot.alloc(totals, "mesh scan totals")))
-        return rc;
-    c->meshItems = std::move(items);
-    c->meshCounts = std::move(cnt);
-    c->meshTotals = std::move(tot);
-    return VH_OK;
-}
-
+// one pass of mesh_block_kernel over the listed blocks: the count pass, or the emitting one
 template <bool kApron>
-static void mesh_launch_blocks(vh_context *c, const FrameParams &fp, const DevPtrs &dp, unsigned grid, const unsigned long long *numItems,
-                               uint32_t listCapacity, uint32_t *blockCount, const unsigned long long *tileBase, bool emit,
+static void mesh_launch_blocks(vh_context *c, const FrameParams &fp, const DevPtrs &dp, const BlockListScratch &sc, bool emit,
                                unsigned long long capacity, float *positions, float *normals)
 {
-    const int4 *items = c->meshItems;
+    const unsigned grid = (unsigned)std::min<size_t>(sc.listCapacity, 8192);
+    const int4 *items = sc.items;
+    const unsigned long long *numItems = sc.result, *tileBase = sc.blockTiles;
     if (!emit)
         hipLaunchKernelGGL((mesh_block_kernel<kApron, false, false>), dim3(grid), dim3(256), 0, c->stream, fp, dp, items, numItems,
-                           listCapacity, blockCount, tileBase, 0ull, (float *)nullptr, (float *)nullptr);
+                           sc.listCapacity, sc.blockCount, tileBase, 0ull, (float *)nullptr, (float *)nullptr);
     else if (normals)
         hipLaunchKernelGGL((mesh_block_kernel<kApron, true, true>), dim3(grid), dim3(256), 0, c->stream, fp, dp, items, numItems,
-                           listCapacity, blockCount, tileBase, capacity, positions, normals);
+                           sc.listCapacity, sc.blockCount, tileBase, capacity, positions, normals);
     else
         hipLaunchKernelGGL((mesh_block_kernel<kApron, true, false>), dim3(grid), dim3(256), 0, c->stream, fp, dp, items, numItems,
-                           listCapacity, blockCount, tileBase, capacity, positions, normals);
+                           sc.listCapacity, sc.blockCount, tileBase, capacity, positions, normals);
 }
 
 extern "C" int vh_extract_mesh(vh_context *c, const vh_mesh_region *region, uint64_t capacity_triangles, float *d_positions,
@@ -49,47 +30,17 @@ extern "C" int vh_extract_mesh(vh_context *c, const vh_mesh_region *region, uint
     DeviceGuard guard(c->device);
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }      // the frames queued so far are part of the model
 
-    MeshRegion rg;
-    for (int a = 0; a < 3; ++a) {
-        rg.lo[a] = region ? region->block_lo[a] : INT32_MIN;
-        rg.hi[a] = region ? region->block_hi[a] : INT32_MAX;
-    }
-    const size_t slices = ((size_t)c->ownedBuckets + kMeshSliceBuckets - 1) / kMeshSliceBuckets;
-    // a table holds at most numVoxelBlocks blocks, a view table one per imported record
-    const size_t blocks = std::max<size_t>(1, std::min<size_t>(c->numEntries, c->viewBlocks ? (size_t)c->viewCount : (size_t)c->params.numVoxelBlocks));
-    { const int rc = mesh_reserve(c, slices, blocks); if (rc != VH_OK) return rc; }
-    const uint32_t listCapacity = (uint32_t)c->meshItems.size();
-    uint32_t *sliceCount = c->meshCounts, *blockCount = sliceCount + slices;
-    unsigned long long *sliceTiles = c->meshTotals;
-    unsigned long long *blockTiles = sliceTiles + (slices + kMeshScanTile - 1) / kMeshScanTile;
-    unsigned long long *result = blockTiles + (c->meshItems.size() + kMeshScanTile - 1) / kMeshScanTile;   // {listed blocks, triangles}
-
-    FrameParams fp = c->fp;
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);     // view table: voxels live in the records
+    const FrameParams fp = c->fp;
+    const DevPtrs dp = model_ptrs(c);
     hipStream_t s = c->stream;
-    const unsigned listGrid = (unsigned)grid_for(slices, 4), sliceTileGrid = (unsigned)grid_for(slices, kMeshScanTile);
-    hipLaunchKernelGGL(mesh_list_kernel<false>, dim3(listGrid), dim3(256), 0, s, fp, dp, rg, c->ownedBuckets, (uint32_t)slices,
-                       sliceCount, (const unsigned long long *)sliceTiles, (int4 *)c->meshItems, listCapacity);
-    hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(sliceTileGrid), dim3(256), 0, s, sliceCount, (const unsigned long long *)nullptr,
-                       (uint32_t)slices, sliceTiles);
-    hipLaunchKernelGGL(mesh_scan_totals_kernel, dim3(1), dim3(256), 0, s, sliceTiles, (const unsigned long long *)nullptr,
-                       (uint32_t)slices, (unsigned long long)listCapacity, result);
-    hipLaunchKernelGGL(mesh_list_kernel<true>, dim3(listGrid), dim3(256), 0, s, fp, dp, rg, c->ownedBuckets, (uint32_t)slices,
-                       sliceCount, (const unsigned long long *)sliceTiles, (int4 *)c->meshItems, listCapacity);
+    BlockListScratch sc;
+    { const int rc = list_blocks(c, fp, dp, block_box(region), true, sc); if (rc != VH_OK) return rc; }
+    unsigned long long *result = sc.result;            // {listed blocks, triangles}
 
-    const unsigned blockGrid = (unsigned)std::min<size_t>(c->meshItems.size(), 8192);
-    const unsigned blockTileGrid = (unsigned)grid_for(c->meshItems.size(), kMeshScanTile);
-    const bool apron = c->meshVariant == 0;
-    if (apron) mesh_launch_blocks<true>(c, fp, dp, blockGrid, result, listCapacity, blockCount, blockTiles, false, 0, nullptr, nullptr);
-    else mesh_launch_blocks<false>(c, fp, dp, blockGrid, result, listCapacity, blockCount, blockTiles, false, 0, nullptr, nullptr);
-    hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(blockTileGrid), dim3(256), 0, s, blockCount, (const unsigned long long *)result, 0u,
-                       blockTiles);
-    hipLaunchKernelGGL(mesh_scan_totals_kernel, dim3(1), dim3(256), 0, s, blockTiles, (const unsigned long long *)result, 0u, ~0ull, result + 1);
-    if (capacity_triangles > 0) {
-        if (apron) mesh_launch_blocks<true>(c, fp, dp, blockGrid, result, listCapacity, blockCount, blockTiles, true, capacity_triangles, d_positions, d_normals);
-        else mesh_launch_blocks<false>(c, fp, dp, blockGrid, result, listCapacity, blockCount, blockTiles, true, capacity_triangles, d_positions, d_normals);
-    }
+    const auto pass = c->meshVariant == 0 ? mesh_launch_blocks<true> : mesh_launch_blocks<false>;
+    pass(c, fp, dp, sc, false, 0, nullptr, nullptr);
+    scan_counts(s, sc.blockCount, result, sc.listCapacity, sc.blockTiles, ~0ull, result + 1);
+    if (capacity_triangles > 0) pass(c, fp, dp, sc, true, capacity_triangles, d_positions, d_normals);
     VH_HIP(hipGetLastError());
     unsigned long long h[2] = {0, 0};
     VH_HIP(hipMemcpyAsync(h, result, sizeof h, hipMemcpyDeviceToHost, s));
@@ -124,19 +75,34 @@ extern "C" int vh_extract_mesh_host(vh_context *c, const vh_mesh_region *region,
 // ---------------------------------------------------------------------------
 // the indexed form
 // ---------------------------------------------------------------------------
-// Scratch of the indexed call alone, beside mesh_reserve's: 2 KB of words and a vertex count per listed block, and the map
-// from a block's ptr >> 9 to its list position (unique per block: heap blocks lie 512 voxels apart, view records 514).
-static int mesh_reserve_indexed(vh_context *c, size_t blocks, size_t listPosSize)
+// Scratch of the indexed call alone, beside the block list's, and the only place that knows its layout.  meshWords: 2 KB of
+// words per listed block, a vertex count per block, then the map from a block's ptr >> 9 to its list position.
+// meshVertexTotals: the vertex scan's tile totals, then the call's three result words.
+struct IndexedMeshScratch {
+    uint32_t *word = nullptr, *vertexCount = nullptr, *listPos = nullptr;
+    uint32_t listPosSize = 0;
+    unsigned long long *vertexTiles = nullptr, *result = nullptr;
+};
+
+static int mesh_reserve_indexed(vh_context *c, size_t blocks, IndexedMeshScratch &ix)
 {
-    const size_t words = blocks * 512 + blocks + listPosSize, totals = (blocks + kMeshScanTile - 1) / kMeshScanTile + 3;
-    if (c->meshWords.size() >= words && c->meshVertexTotals.size() >= totals) return VH_OK;
-    VH_HIP(hipStreamSynchronize(c->stream));
-    DevBuf<uint32_t> w;
-    DevBuf<unsigned long long> tot;
-    int rc;
-    if ((rc = w.alloc(words, "mesh vertex words")) || (rc = tot.alloc(totals, "mesh vertex scan totals"))) return rc;
-    c->meshWords = std::move(w);
-    c->meshVertexTotals = std::move(tot);
+    const size_t listPosSize = ptr_map_size(c);
+    const size_t words = blocks * 512 + blocks + listPosSize, totals = scan_tiles(blocks) + 3;
+    if (c->meshWords.size() < words || c->meshVertexTotals.size() < totals) {
+        VH_HIP(hipStreamSynchronize(c->stream));
+        DevBuf<uint32_t> w;
+        DevBuf<unsigned long long> tot;
+        int rc;
+        if ((rc = w.alloc(words, "mesh vertex words")) || (rc = tot.alloc(totals, "mesh vertex scan totals"))) return rc;
+        c->meshWords = std::move(w);
+        c->meshVertexTotals = std::move(tot);
+    }
+    ix.word = c->meshWords;
+    ix.vertexCount = ix.word + blocks * 512;
+    ix.listPos = ix.vertexCount + blocks;
+    ix.listPosSize = (uint32_t)listPosSize;
+    ix.vertexTiles = c->meshVertexTotals;
+    ix.result = ix.vertexTiles + scan_tiles(blocks);
     return VH_OK;
 }
 
@@ -153,63 +119,36 @@ extern "C" int vh_extract_mesh_indexed(vh_context *c, const vh_mesh_region *regi
     DeviceGuard guard(c->device);
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }
 
-    MeshRegion rg, grown;                  // the cells' blocks; the vertices' blocks: one more towards +
-    for (int a = 0; a < 3; ++a) {
-        rg.lo[a] = grown.lo[a] = region ? region->block_lo[a] : INT32_MIN;
-        rg.hi[a] = region ? region->block_hi[a] : INT32_MAX;
-        grown.hi[a] = mesh_grow(rg.hi[a]);
-    }
-    const size_t slices = ((size_t)c->ownedBuckets + kMeshSliceBuckets - 1) / kMeshSliceBuckets;
-    const size_t blocks = std::max<size_t>(1, std::min<size_t>(c->numEntries, c->viewBlocks ? (size_t)c->viewCount : (size_t)c->params.numVoxelBlocks));
-    const size_t listPosSize = c->viewBlocks ? (((size_t)c->viewCount * 514 + 2) >> 9) + 1 : (size_t)c->params.numVoxelBlocks;
-    { const int rc = mesh_reserve(c, slices, blocks); if (rc != VH_OK) return rc; }
-    const size_t listed = c->meshItems.size();
-    { const int rc = mesh_reserve_indexed(c, listed, listPosSize); if (rc != VH_OK) return rc; }
-    const uint32_t listCapacity = (uint32_t)listed;
-    const size_t tiles = (listed + kMeshScanTile - 1) / kMeshScanTile;
-    uint32_t *sliceCount = c->meshCounts, *triangleCount = sliceCount + slices;
-    unsigned long long *sliceTiles = c->meshTotals;
-    unsigned long long *triangleTiles = sliceTiles + (slices + kMeshScanTile - 1) / kMeshScanTile;
-    uint32_t *word = c->meshWords, *vertexCount = word + listed * 512, *listPos = vertexCount + listed;
-    unsigned long long *vertexTiles = c->meshVertexTotals, *result = vertexTiles + tiles;    // {listed blocks, vertices, triangles}
+    const BlockBox rg = block_box(region);  // the cells' blocks
+    BlockBox grown = rg;                    // the vertices' blocks: one more towards +
+    for (int a = 0; a < 3; ++a) grown.hi[a] = mesh_grow(rg.hi[a]);
+    BlockListScratch sc;
+    IndexedMeshScratch ix;
+    { const int rc = block_list_reserve(c, sc); if (rc != VH_OK) return rc; }
+    { const int rc = mesh_reserve_indexed(c, sc.listCapacity, ix); if (rc != VH_OK) return rc; }
+    sc.result = ix.result;                  // one set of result words for the call: {listed blocks, vertices, triangles}
+    const unsigned long long *result = ix.result;
+    uint32_t *triangleCount = sc.blockCount;
+    unsigned long long *triangleTiles = sc.blockTiles;
 
-    FrameParams fp = c->fp;
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);
+    const FrameParams fp = c->fp;
+    const DevPtrs dp = model_ptrs(c);
     hipStream_t s = c->stream;
-    const unsigned listGrid = (unsigned)grid_for(slices, 4), sliceTileGrid = (unsigned)grid_for(slices, kMeshScanTile);
-    hipLaunchKernelGGL(mesh_list_kernel<false>, dim3(listGrid), dim3(256), 0, s, fp, dp, grown, c->ownedBuckets, (uint32_t)slices,
-                       sliceCount, (const unsigned long long *)sliceTiles, (int4 *)c->meshItems, listCapacity);
-    hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(sliceTileGrid), dim3(256), 0, s, sliceCount, (const unsigned long long *)nullptr,
-                       (uint32_t)slices, sliceTiles);
-    hipLaunchKernelGGL(mesh_scan_totals_kernel, dim3(1), dim3(256), 0, s, sliceTiles, (const unsigned long long *)nullptr,
-                       (uint32_t)slices, (unsigned long long)listCapacity, result);
-    hipLaunchKernelGGL(mesh_list_kernel<true>, dim3(listGrid), dim3(256), 0, s, fp, dp, grown, c->ownedBuckets, (uint32_t)slices,
-                       sliceCount, (const unsigned long long *)sliceTiles, (int4 *)c->meshItems, listCapacity);
+    { const int rc = list_blocks(c, fp, dp, grown, true, sc); if (rc != VH_OK) return rc; }
 
-    const unsigned blockGrid = (unsigned)std::min<size_t>(listed, 8192), tileGrid = (unsigned)grid_for(listed, kMeshScanTile);
-    const int4 *items = c->meshItems;
-    hipLaunchKernelGGL(mesh_indexed_count_kernel, dim3(blockGrid), dim3(256), 0, s, fp, dp, rg, items, (const unsigned long long *)result,
-                       listCapacity, listPos, (uint32_t)listPosSize, word, vertexCount, triangleCount);
-    hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(tileGrid), dim3(256), 0, s, vertexCount, (const unsigned long long *)result, 0u, vertexTiles);
-    hipLaunchKernelGGL(mesh_scan_totals_kernel, dim3(1), dim3(256), 0, s, vertexTiles, (const unsigned long long *)result, 0u, ~0ull, result + 1);
-    hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(tileGrid), dim3(256), 0, s, triangleCount, (const unsigned long long *)result, 0u, triangleTiles);
-    hipLaunchKernelGGL(mesh_scan_totals_kernel, dim3(1), dim3(256), 0, s, triangleTiles, (const unsigned long long *)result, 0u, ~0ull, result + 2);
+    const unsigned blockGrid = (unsigned)std::min<size_t>(sc.listCapacity, 8192);
+    const int4 *items = sc.items;
+    hipLaunchKernelGGL(mesh_indexed_count_kernel, dim3(blockGrid), dim3(256), 0, s, fp, dp, rg, items, result, sc.listCapacity,
+                       ix.listPos, ix.listPosSize, ix.word, ix.vertexCount, triangleCount);
+    scan_counts(s, ix.vertexCount, result, sc.listCapacity, ix.vertexTiles, ~0ull, ix.result + 1);
+    scan_counts(s, triangleCount, result, sc.listCapacity, triangleTiles, ~0ull, ix.result + 2);
     if (capacity_vertices > 0 || capacity_triangles > 0) {
-        if (d_vertex_normals)
-            hipLaunchKernelGGL(mesh_indexed_emit_kernel<true>, dim3(blockGrid), dim3(256), 0, s, fp, dp, rg, items,
-                               (const unsigned long long *)result, listCapacity, (const uint32_t *)listPos, (uint32_t)listPosSize,
-                               (const uint32_t *)word, (const uint32_t *)vertexCount, (const unsigned long long *)vertexTiles,
-                               (const uint32_t *)triangleCount, (const unsigned long long *)triangleTiles,
-                               (unsigned long long)capacity_vertices, (unsigned long long)capacity_triangles, d_vertices,
-                               d_vertex_normals, d_indices);
-        else
-            hipLaunchKernelGGL(mesh_indexed_emit_kernel<false>, dim3(blockGrid), dim3(256), 0, s, fp, dp, rg, items,
-                               (const unsigned long long *)result, listCapacity, (const uint32_t *)listPos, (uint32_t)listPosSize,
-                               (const uint32_t *)word, (const uint32_t *)vertexCount, (const unsigned long long *)vertexTiles,
-                               (const uint32_t *)triangleCount, (const unsigned long long *)triangleTiles,
-                               (unsigned long long)capacity_vertices, (unsigned long long)capacity_triangles, d_vertices,
-                               d_vertex_normals, d_indices);
+        const auto emit = d_vertex_normals ? mesh_indexed_emit_kernel<true> : mesh_indexed_emit_kernel<false>;
+        hipLaunchKernelGGL(emit, dim3(blockGrid), dim3(256), 0, s, fp, dp, rg, items, result, sc.listCapacity,
+                           (const uint32_t *)ix.listPos, ix.listPosSize, (const uint32_t *)ix.word, (const uint32_t *)ix.vertexCount,
+                           (const unsigned long long *)ix.vertexTiles, (const uint32_t *)triangleCount,
+                           (const unsigned long long *)triangleTiles, (unsigned long long)capacity_vertices,
+                           (unsigned long long)capacity_triangles, d_vertices, d_vertex_normals, d_indices);
     }
     VH_HIP(hipGetLastError());
     unsigned long long h[3] = {0, 0, 0};

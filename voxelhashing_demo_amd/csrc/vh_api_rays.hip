@@ -25,8 +25,7 @@ extern "C" int vh_cast_rays(vh_context *c, uint64_t n, const vh_ray *d_rays, con
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }      // the frames queued so far are part of the model
 
     FrameParams fp = c->fp;
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);     // view table: voxels live in the records
+    DevPtrs dp = model_ptrs(c);
     const unsigned grid = ((unsigned)grid_for((size_t)n, kRaysBlock) + 7u) & ~7u;      // (cast_rays_kernel: a multiple of the 8 XCDs)
     hipLaunchKernelGGL(cast_rays_kernel, dim3(grid), dim3(kRaysBlock), 0, c->stream, fp, dp, plane, (uint32_t)n,
                        reinterpret_cast<const float4 *>(d_rays), d_t, d_normals, d_voxels);

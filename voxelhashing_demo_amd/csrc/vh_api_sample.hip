@@ -15,8 +15,7 @@ extern "C" int vh_sample_sdf(vh_context *c, int32_t mode, uint64_t n, const floa
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }      // the frames queued so far are part of the model
 
     FrameParams fp = c->fp;
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);     // view table: voxels live in the records
+    DevPtrs dp = model_ptrs(c);
     const unsigned grid = (unsigned)grid_for((size_t)n, 256);
     hipLaunchKernelGGL(sample_points_kernel, dim3(grid), dim3(256), 0, c->stream, fp, dp, (int)mode, (uint32_t)n, d_points, d_sdf,
                        d_weight, d_gradient);
@@ -74,8 +73,7 @@ extern "C" int vh_sample_lattice(vh_context *c, const int32_t lo[3], const int32
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }
 
     FrameParams fp = c->fp;
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);
+    DevPtrs dp = model_ptrs(c);
     const unsigned grid = (unsigned)std::min<unsigned long long>(bricks, 1ull << 20);
     hipLaunchKernelGGL(sample_lattice_kernel, dim3(grid), dim3(256), 0, c->stream, fp, dp, box, bricks, d_sdf, d_weight);
     VH_HIP(hipGetLastError());

@@ -1,12 +1,12 @@
 // vh_api_stream.hip -- C-ABI, block streaming: vh_stream_out, vh_stream_in and their _host forms (kernels: vh_stream.hip).
 // Included by vh_api.hip after everything else (same translation unit: shares fail(), VH_HIP, DeviceGuard, launch(), settle(),
-// mesh_reserve() and the mesh scans, sweep_and_release(), ensure_candidates(), bin_alloc_rounds(), ensure_color()).
+// the block list and its scans, reserve_scratch(), sweep_and_release(), ensure_candidates(), bin_alloc_rounds(), ensure_color()).
 // Both calls read counts back: they synchronise the context's stream.
 
 // The records one vh_stream_in takes: 2^24 (64 GiB of voxels); beyond it the call is refused before anything changes.
 constexpr unsigned long long kStreamMaxRecords = 1ull << 24;
 
-static int stream_region(const vh_stream_region *region, StreamRegion &rg)
+static int stream_region(const vh_stream_region *region, float voxelSize, StreamSelect &rg)
 {
     if (region->kind != VH_STREAM_BOX && region->kind != VH_STREAM_SPHERE) return fail(VH_ERR_INVALID_ARGUMENT, "unknown region kind");
     if (!std::isfinite(region->radius) || !(region->radius >= 0.0f)) return fail(VH_ERR_INVALID_ARGUMENT, "radius must be finite and >= 0");
@@ -15,21 +15,13 @@ static int stream_region(const vh_stream_region *region, StreamRegion &rg)
     rg.kind = region->kind;
     rg.invert = region->invert != 0;
     for (int a = 0; a < 3; ++a) {
-        rg.lo[a] = region->block_lo[a];
-        rg.hi[a] = region->block_hi[a];
+        rg.box.lo[a] = region->block_lo[a];
+        rg.box.hi[a] = region->block_hi[a];
         rg.centre[a] = region->centre[a];
     }
     rg.radius2 = region->radius * region->radius;        // (float32, rounded once: the rule's right-hand side)
+    rg.voxelSize = voxelSize;
     return VH_OK;
-}
-
-// a scratch buffer of at least `count` elements; what still uses a smaller one is synchronised away first
-template <class T>
-static int stream_reserve(vh_context *c, DevBuf<T> &buf, size_t count, const char *what)
-{
-    if (buf.size() >= count && buf.get()) return VH_OK;
-    VH_HIP(hipStreamSynchronize(c->stream));
-    return buf.alloc(count, what);
 }
 
 extern "C" int vh_stream_out(vh_context *c, const vh_stream_region *region, uint64_t capacity, vh_view_record *d_records,
@@ -39,34 +31,19 @@ extern "C" int vh_stream_out(vh_context *c, const vh_stream_region *region, uint
     if (!c || !region || !selected_out || !written_out) return fail(VH_ERR_INVALID_ARGUMENT, "null argument");
     if (capacity > 0 && !d_records) return fail(VH_ERR_INVALID_ARGUMENT, "a capacity needs a record buffer");
     if (c->viewBlocks) return fail(VH_ERR_INVALID_ARGUMENT, "a view table owns no blocks");
-    StreamRegion rg;
-    int rc = stream_region(region, rg);
+    StreamSelect rg;
+    int rc = stream_region(region, c->fp.voxelSize, rg);
     if (rc != VH_OK) return rc;
     DeviceGuard guard(c->device);
     if ((rc = settle(c)) != VH_OK) return rc;          // the frames queued so far are part of the model
 
-    // 1. the ordered block list: the mesh's count, scan and write (its scratch and its scans) with the region as predicate
-    const size_t slices = ((size_t)c->ownedBuckets + kMeshSliceBuckets - 1) / kMeshSliceBuckets;
-    const size_t blocks = std::max<size_t>(1, std::min<size_t>(c->numEntries, (size_t)c->params.numVoxelBlocks));
-    if ((rc = mesh_reserve(c, slices, blocks)) != VH_OK) return rc;
-    const uint32_t listCapacity = (uint32_t)c->meshItems.size();
-    uint32_t *sliceCount = c->meshCounts;
-    unsigned long long *sliceTiles = c->meshTotals;
-    unsigned long long *result = sliceTiles + (slices + kMeshScanTile - 1) / kMeshScanTile + (c->meshItems.size() + kMeshScanTile - 1) / kMeshScanTile;
+    // 1. the ordered block list with the region as predicate; the count-only call stops at its length
     hipStream_t s = c->stream;
-    const unsigned listGrid = (unsigned)grid_for(slices, 4), sliceTileGrid = (unsigned)grid_for(slices, kMeshScanTile);
-    hipLaunchKernelGGL(stream_list_kernel<false>, dim3(listGrid), dim3(256), 0, s, c->fp, c->dp, rg, c->ownedBuckets, (uint32_t)slices,
-                       sliceCount, (const unsigned long long *)sliceTiles, (int4 *)c->meshItems, listCapacity);
-    hipLaunchKernelGGL(mesh_scan_tiles_kernel, dim3(sliceTileGrid), dim3(256), 0, s, sliceCount, (const unsigned long long *)nullptr,
-                       (uint32_t)slices, sliceTiles);
-    hipLaunchKernelGGL(mesh_scan_totals_kernel, dim3(1), dim3(256), 0, s, sliceTiles, (const unsigned long long *)nullptr,
-                       (uint32_t)slices, (unsigned long long)listCapacity, result);
-    if (capacity > 0)
-        hipLaunchKernelGGL(stream_list_kernel<true>, dim3(listGrid), dim3(256), 0, s, c->fp, c->dp, rg, c->ownedBuckets, (uint32_t)slices,
-                           sliceCount, (const unsigned long long *)sliceTiles, (int4 *)c->meshItems, listCapacity);
+    BlockListScratch sc;
+    if ((rc = list_blocks(c, c->fp, c->dp, rg, capacity > 0, sc)) != VH_OK) return rc;
     VH_HIP(hipGetLastError());
     unsigned long long selected = 0;
-    VH_HIP(hipMemcpyAsync(&selected, result, sizeof selected, hipMemcpyDeviceToHost, s));
+    VH_HIP(hipMemcpyAsync(&selected, sc.result, sizeof selected, hipMemcpyDeviceToHost, s));
     VH_HIP(hipStreamSynchronize(s));
     if ((rc = check_spin_timeouts(c)) != VH_OK) return rc;
     const uint64_t written = std::min<uint64_t>(selected, capacity);       // (at most the list's capacity: the scan's total is capped)
@@ -77,12 +54,12 @@ extern "C" int vh_stream_out(vh_context *c, const vh_stream_region *region, uint
     // 2. the records, then 3. the removal: vh_delete_blocks on the listed keys (the list's records begin with the key)
     // (timed as view_export_ms when profiling is on: the record packing of this call)
     rc = launch(c, kPhaseViewExport, stream_pack_kernel, dim3((unsigned)std::min<uint64_t>(written, 2048)), dim3(256), c->dp,
-                (const uint32_t *)c->color.get(), (const int4 *)c->meshItems.get(), (uint32_t)written,
+                (const uint32_t *)c->color.get(), (const int4 *)sc.items, (uint32_t)written,
                 reinterpret_cast<uint8_t *>(d_records), d_colors);
     if (rc != VH_OK) return rc;
     if ((rc = vh_reset_mutexes(c)) != VH_OK) return rc;
     rc = launch(c, kPhaseGc, gc_mark_keys_kernel, dim3((unsigned)grid_for((size_t)written, 256)), dim3(256), c->fp, c->dp,
-                (const int4 *)c->meshItems.get(), (int32_t)written);
+                (const int4 *)sc.items, (int32_t)written);
     if (rc == VH_OK) rc = sweep_and_release(c);
     if (rc != VH_OK) return rc;
     VH_HIP(hipStreamSynchronize(s));
@@ -106,10 +83,10 @@ extern "C" int vh_stream_in(vh_context *c, uint64_t n, const vh_view_record *d_r
     if (rc != VH_OK) return rc;
     StreamScratch &ss = c->streaming;
     MergeScratch &ms = c->merge;                       // the bin and the rounds' counts are vh_merge's
-    if ((rc = stream_reserve(c, ss.totals, 4, "stream totals")) != VH_OK) return rc;
-    if (!d_status && (rc = stream_reserve(c, ss.status, (size_t)n, "stream statuses")) != VH_OK) return rc;
-    if ((rc = stream_reserve(c, ms.words, kMergeWords, "merge counts")) != VH_OK) return rc;
-    if ((rc = stream_reserve(c, ms.bin, (size_t)n + 1, "stream key bin")) != VH_OK) return rc;
+    if ((rc = reserve_scratch(c, ss.totals, 4, "stream totals")) != VH_OK) return rc;
+    if (!d_status && (rc = reserve_scratch(c, ss.status, (size_t)n, "stream statuses")) != VH_OK) return rc;
+    if ((rc = reserve_scratch(c, ms.words, kMergeWords, "merge counts")) != VH_OK) return rc;
+    if ((rc = reserve_scratch(c, ms.bin, (size_t)n + 1, "stream key bin")) != VH_OK) return rc;
     int32_t *status = d_status ? d_status : ss.status.get();
     int4 *bin = ms.bin;
     const uint8_t *records = reinterpret_cast<const uint8_t *>(d_records);
@@ -172,8 +149,8 @@ extern "C" int vh_stream_out_host(vh_context *c, const vh_stream_region *region,
     if (want == 0) return VH_OK;
     DeviceGuard guard(c->device);
     StreamScratch &ss = c->streaming;
-    if ((rc = stream_reserve(c, ss.records, (size_t)want * sizeof(vh_view_record), "stream records")) != VH_OK) return rc;
-    if (h_colors && (rc = stream_reserve(c, ss.colors, (size_t)want * kBlockVoxels, "stream colours")) != VH_OK) return rc;
+    if ((rc = reserve_scratch(c, ss.records, (size_t)want * sizeof(vh_view_record), "stream records")) != VH_OK) return rc;
+    if (h_colors && (rc = reserve_scratch(c, ss.colors, (size_t)want * kBlockVoxels, "stream colours")) != VH_OK) return rc;
     rc = vh_stream_out(c, region, want, reinterpret_cast<vh_view_record *>(ss.records.get()), h_colors ? ss.colors.get() : nullptr,
                        selected_out, written_out);
     if (rc != VH_OK) return rc;
@@ -195,9 +172,9 @@ extern "C" int vh_stream_in_host(vh_context *c, uint64_t n, const vh_view_record
     DeviceGuard guard(c->device);
     StreamScratch &ss = c->streaming;
     int rc;
-    if ((rc = stream_reserve(c, ss.records, (size_t)n * sizeof(vh_view_record), "stream records")) != VH_OK) return rc;
-    if (h_colors && (rc = stream_reserve(c, ss.colors, (size_t)n * kBlockVoxels, "stream colours")) != VH_OK) return rc;
-    if (h_status && (rc = stream_reserve(c, ss.hostStatus, (size_t)n, "stream statuses")) != VH_OK) return rc;
+    if ((rc = reserve_scratch(c, ss.records, (size_t)n * sizeof(vh_view_record), "stream records")) != VH_OK) return rc;
+    if (h_colors && (rc = reserve_scratch(c, ss.colors, (size_t)n * kBlockVoxels, "stream colours")) != VH_OK) return rc;
+    if (h_status && (rc = reserve_scratch(c, ss.hostStatus, (size_t)n, "stream statuses")) != VH_OK) return rc;
     VH_HIP(hipMemcpyAsync(ss.records, h_records, (size_t)n * sizeof(vh_view_record), hipMemcpyHostToDevice, c->stream));
     if (h_colors) VH_HIP(hipMemcpyAsync(ss.colors, h_colors, (size_t)n * kBlockVoxels * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     rc = vh_stream_in(c, n, reinterpret_cast<const vh_view_record *>(ss.records.get()), h_colors ? ss.colors.get() : nullptr,

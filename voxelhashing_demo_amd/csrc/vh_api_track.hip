@@ -54,8 +54,7 @@ static SdfTrackParams sdf_track_params(const vh_icp *p, const float *pose, const
 static void sdf_round(vh_context *c, vh_icp *p, const SdfTrackParams &tp, const vh_float4 *d_input, const uint32_t *d_rgba, bool photo,
                       const SdfTrackMaps *maps, int useState, int solve)
 {
-    DevPtrs dp = c->dp;
-    if (c->viewBlocks) dp.blocks = const_cast<Voxel *>(c->viewBlocks);     // view table: voxels live in the records
+    DevPtrs dp = model_ptrs(c);
     const auto kernel = maps ? (photo ? sdf_round_kernel<true, true> : sdf_round_kernel<true, false>)
                              : (photo ? sdf_round_kernel<false, true> : sdf_round_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(p->blocks), dim3(kIcpThreads), 0, c->stream, c->fp, dp, tp, reinterpret_cast<const float4 *>(d_input),

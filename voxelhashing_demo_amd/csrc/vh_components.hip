@@ -1,12 +1,12 @@
 // vh_components.hip -- connected pieces of the fused model: vh_components, vh_remove_components.
-// Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after vh_sample.hip (mesh list and scans: vh_mesh.hip,
+// Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after vh_sample.hip (block list and scans: vh_blocklist.hip,
 // lookup_block: vh_raycast.hip, sample_judge / LatticeBox: vh_sample.hip).
 //
 // The rule (include/voxelhash.h, tests/components_ref.py) is in integers: a node is a valid voxel of the target class in a
 // listed block, its id is rank * 512 + voxel index (rank = position of its block in the mesh's ordered block list), an edge
 // joins A and A + o for o in the three axis units (connectivity 6) or in {0,1}^3 \ {0} (14), a component's root is its node
 // of least id.  A union-find whose parent never grows: parent[id] <= id always, a non-root's parent is strictly less.
-//   (mesh_list_kernel / mesh_scan_*   the ordered block list with the region as predicate)
+//   (vh_blocklist.hip      the ordered block list with the region, a BlockBox, as predicate)
 //   comp_local_kernel      one workgroup pass per listed block: classify the 512 voxels, unite the pairs inside the block
 //                          in LDS, parent[id] = least node of the block's own component (none: VH_COMPONENT_NONE);
 //                          rank[ptr >> 9] = list position
@@ -15,7 +15,7 @@
 //   comp_flatten_kernel    parent[id] = root for every node; one bit per root, roots per block
 //   comp_count_kernel      nodes per root: summed per workgroup in an LDS table keyed by root, then one integer atomic per
 //                          root the block saw, added onto the root's own parent word (so parent[root] = root + size)
-//   (mesh_scan_*           exclusive scan of the roots per block: a root's component index)
+//   (block_scan_*          exclusive scan of the roots per block: a root's component index)
 //   comp_records_kernel    the records in root order; the largest size
 //   comp_labels_kernel     a box of the lattice: sample_lattice_kernel's brick pass, the component index per voxel
 //   comp_remove_kernel     vh_remove_components: the voxels (and colour words) of the small components cleared, the keys of
@@ -210,7 +210,7 @@ __device__ __forceinline__ unsigned long long comp_index(const unsigned long lon
     uint32_t before = 0;
     for (uint32_t w = 0; w < (v >> 6); ++w) before += (uint32_t)__popcll(bits[w]);
     before += (uint32_t)__popcll(bits[v >> 6] & ((1ull << (v & 63u)) - 1ull));
-    return rootTiles[b / (uint32_t)kMeshScanTile] + rootOffset[b] + before;
+    return scanned_at(rootTiles, rootOffset, b) + before;
 }
 
 // Sizes.  A root's word is read by nobody in this launch (its block knows it as a root from rootBits), every other node's word

@@ -19,6 +19,8 @@
 //   vh_blocks.hip      block silhouettes: per-pixel nearest front / farthest back face of the allocated
 //                      blocks' cubes (SDFRenderer::drawToFrontAndBack, SDFRenderer.cpp:165-208)
 //   vh_gc.hip          block deletion / garbage collection (deleteVoxelEntry :544-604 done correctly)
+//   vh_blocklist.hip   the ordered block list of a region (count -> scan -> write over the bucket range) and the two-level
+//                      scan: the front end of the mesh, the components and block streaming (no counterpart in the reference)
 //   vh_mesh.hip        iso-surface extraction: ordered block list, marching tetrahedra per block behind a 9^3 apron in
 //                      LDS, count -> scan -> emit (no counterpart in the reference)
 //   vh_sample.hip      the model as a distance field: sdf / weight / gradient at world points (one point per lane),
@@ -63,6 +65,7 @@
 #include "vh_blocks.hip"
 #include "vh_preprocess.hip"
 #include "vh_icp.hip"
+#include "vh_blocklist.hip"
 #include "vh_mesh.hip"
 #include "vh_sample.hip"
 #include "vh_esdf.hip"

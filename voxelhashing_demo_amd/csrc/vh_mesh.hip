@@ -1,14 +1,12 @@
 // vh_mesh.hip -- iso-surface extraction: the fused TSDF as a triangle list (vh_extract_mesh; DESIGN.md "mesh").
-// Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after vh_raycast.hip (lookup_block).
+// Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after vh_raycast.hip (lookup_block) and vh_blocklist.hip.
 //
 // Marching tetrahedra on the Kuhn split of every cell whose eight corner voxels are valid (block allocated, weight > 0;
 // inside iff sdf <= 0).  The output order is fixed -- blocks in ascending entry index, cells in ascending voxel index,
 // tetrahedra 0..5, triangles in table order -- so nothing here takes an output slot with a bare atomicAdd:
-//   mesh_list_kernel<false>   per-wave slice of the bucket range: allocated entries (inside the region) counted
-//   mesh_scan_*               exclusive scan of the slice counts
-//   mesh_list_kernel<true>    the same walk, entries written in order: the block list
+//   (vh_blocklist.hip              the ordered block list with the region, a BlockBox, as predicate)
 //   mesh_block_kernel<.., false>   one workgroup pass per listed block: 9^3 apron in LDS, triangles of the block counted
-//   mesh_scan_*               exclusive scan of the block counts (64-bit offsets)
+//   block_scan_*                   exclusive scan of the block counts (64-bit offsets)
 //   mesh_block_kernel<.., true>    the same pass, triangles (and normals) written at offset[block] + in-block prefix
 #pragma once
 
@@ -16,132 +14,7 @@
 
 namespace vh {
 
-struct MeshRegion { int lo[3], hi[3]; };       // blocks lo <= k < hi
-
-constexpr int kMeshSliceBuckets = 1024;        // buckets per wave of the list walk (16 rounds of 64)
-constexpr int kMeshScanTile = 1024;            // elements per workgroup of the scan's first level
 constexpr int kApronSide = 9, kApronVoxels = 9 * 9 * 9;
-
-// ---------------------------------------------------------------------------
-// the block list
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ bool mesh_listed(const VoxelEntry &e, const MeshRegion &rg)
-{
-    return e.ptr != VH_FREE_BLOCK && e.pos[0] >= rg.lo[0] && e.pos[0] < rg.hi[0] && e.pos[1] >= rg.lo[1] &&
-           e.pos[1] < rg.hi[1] && e.pos[2] >= rg.lo[2] && e.pos[2] < rg.hi[2];
-}
-
-// One lane per bucket, 64 consecutive buckets per round: a lane looks at the slots of its bucket in order (with the overflow
-// list an entry may sit anywhere, so every slot is looked at), and the lanes' counts are put in lane order by a wave scan.
-// kWrite = false: sliceCount[wave] = listed entries of the wave's slice.  kWrite = true: they are written from
-// tileBase[wave / kMeshScanTile] + sliceCount[wave] (what the scan left there) on, as {x, y, z, ptr}.
-template <bool kWrite>
-__global__ __launch_bounds__(256) void mesh_list_kernel(const FrameParams fp, const DevPtrs dp, const MeshRegion rg,
-                                                        uint32_t ownedBuckets, uint32_t numSlices, uint32_t *sliceCount,
-                                                        const unsigned long long *__restrict__ tileBase, int4 *items,
-                                                        uint32_t capacity)
-{
-    const uint32_t lane = threadIdx.x & 63u, slice = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (slice >= numSlices) return;
-    uint32_t running = 0;
-    if (kWrite) running = (uint32_t)tileBase[slice / kMeshScanTile] + sliceCount[slice];
-    const uint32_t first = slice * (uint32_t)kMeshSliceBuckets;
-    for (uint32_t r = 0; r < (uint32_t)kMeshSliceBuckets; r += 64u) {
-        const uint32_t b = first + r + lane;
-        const bool occupied = b < ownedBuckets && ((dp.bucketBits[b >> 5] >> (b & 31u)) & 1u);
-        if (__ballot(occupied) == 0ull) continue;
-        const VoxelEntry *bucket = dp.table + (size_t)b * fp.bucketSize;
-        uint32_t n = 0;
-        if (occupied)
-            for (uint32_t s = 0; s < fp.bucketSize; ++s) n += mesh_listed(bucket[s], rg) ? 1u : 0u;
-        uint32_t incl = n;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if ((int)lane >= d) incl += up;
-        }
-        if (kWrite && n) {
-            uint32_t at = running + incl - n;
-            for (uint32_t s = 0; s < fp.bucketSize; ++s) {
-                const VoxelEntry e = bucket[s];
-                if (!mesh_listed(e, rg)) continue;
-                if (at < capacity) items[at] = make_int4(e.pos[0], e.pos[1], e.pos[2], e.ptr);
-                ++at;
-            }
-        }
-        running += __shfl(incl, 63);
-    }
-    if (!kWrite && lane == 0) sliceCount[slice] = running;
-}
-
-// ---------------------------------------------------------------------------
-// exclusive scan, two levels: tiles of kMeshScanTile counts in place (32-bit prefixes inside the tile, the tile's total as
-// 64 bits), then one workgroup over the tile totals.  n = *nPtr when nPtr is given (a length only the device knows).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t mesh_wg_scan(uint32_t v, uint32_t *sWave, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) sWave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) before += (w < wave) ? sWave[w] : 0u;
-    total = sWave[0] + sWave[1] + sWave[2] + sWave[3];
-    __syncthreads();                      // (sWave is free for the caller's next scan)
-    return before + incl - v;             // exclusive
-}
-
-__global__ __launch_bounds__(256) void mesh_scan_tiles_kernel(uint32_t *counts, const unsigned long long *nPtr, uint32_t nHost,
-                                                              unsigned long long *tileTotal)
-{
-    __shared__ uint32_t sWave[4];
-    const uint32_t n = nPtr ? (uint32_t)*nPtr : nHost;
-    const uint32_t base = blockIdx.x * (uint32_t)kMeshScanTile + threadIdx.x * 4u;
-    if (blockIdx.x * (uint32_t)kMeshScanTile >= n) return;
-    uint32_t v[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[k] = base + k < n ? counts[base + k] : 0u; sum += v[k]; }
-    uint32_t total;
-    uint32_t at = mesh_wg_scan(sum, sWave, total);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { if (base + k < n) counts[base + k] = at; at += v[k]; }
-    if (threadIdx.x == 0) tileTotal[blockIdx.x] = total;
-}
-
-// one workgroup: tileTotal[0 .. ceil(n / kMeshScanTile)) becomes its exclusive scan, *totalOut the sum (at most `cap`: a list's length)
-__global__ __launch_bounds__(256) void mesh_scan_totals_kernel(unsigned long long *tileTotal, const unsigned long long *nPtr,
-                                                               uint32_t nHost, unsigned long long cap, unsigned long long *totalOut)
-{
-    __shared__ unsigned long long sWave[4];
-    const uint32_t n = nPtr ? (uint32_t)*nPtr : nHost;
-    const uint32_t tiles = (n + (uint32_t)kMeshScanTile - 1u) / (uint32_t)kMeshScanTile;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long carry = 0;
-    for (uint32_t t0 = 0; t0 < tiles; t0 += 256u) {
-        const uint32_t t = t0 + threadIdx.x;
-        const unsigned long long v = t < tiles ? tileTotal[t] : 0ull;
-        unsigned long long incl = v;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const unsigned long long up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) sWave[wave] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int w = 0; w < wave; ++w) before += sWave[w];
-        if (t < tiles) tileTotal[t] = before + incl - v;
-        carry += sWave[0] + sWave[1] + sWave[2] + sWave[3];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *totalOut = carry < cap ? carry : cap;
-}
 
 // ---------------------------------------------------------------------------
 // one block
@@ -337,11 +210,11 @@ __global__ __launch_bounds__(256) void mesh_block_kernel(const FrameParams fp, c
         c0 = mesh_cell_count(m0);
         c1 = mesh_cell_count(m1);
         uint32_t total;
-        const uint32_t before = mesh_wg_scan(c0 + c1, sWave, total);      // (its barriers also fence sNb / sApron for the next pass)
+        const uint32_t before = block_wg_scan(c0 + c1, sWave, total);      // (its barriers also fence sNb / sApron for the next pass)
         if (!kEmit) {
             if (tid == 0) blockCount[b] = total;
         } else if (total) {
-            const unsigned long long at = tileBase[b / (uint32_t)kMeshScanTile] + blockCount[b] + before;
+            const unsigned long long at = scanned_at(tileBase, blockCount, b) + before;
             if (kApron) {
                 const MeshApron src{sApron};
                 if (c0) mesh_emit_cell<MeshApron, kNormals>(fp, src, direct, item, 2 * tid, m0, at, capacity, positions, normals);
@@ -362,10 +235,10 @@ __global__ __launch_bounds__(256) void mesh_block_kernel(const FrameParams fp, c
 // the ends are valid with different inside flags and one of the cells that contain the edge (corner 0 at A - o, o disjoint
 // from d) has eight valid corners and lies in a block of the region.  Vertices are ordered by (block of A in list order,
 // voxel index of A, d), so they take their slots by count -> scan -> write like the triangles:
-//   mesh_list_kernel pair          the block list over the region grown by one block towards + (A may sit in a +neighbour)
+//   (vh_blocklist.hip              the block list over the region grown by one block towards +: A may sit in a +neighbour)
 //   mesh_indexed_count_kernel      per listed block: 10^3 apron (local -1..8), a word {prefix << 7 | 7-bit mask} per voxel, the
 //                                  block's vertices and (inside the region) triangles; listPos[ptr / 512] = list position
-//   mesh_scan_*                    twice: vertex offsets, triangle offsets
+//   block_scan_*                   twice: vertex offsets, triangle offsets
 //   mesh_indexed_emit_kernel       vertices (and normals) at base[block] + prefix + popcount(mask below d); indices per
 //                                  triangle in vh_extract_mesh's order, read from the word of A in A's block
 constexpr int kApron10Side = 10, kApron10Voxels = 10 * 10 * 10;
@@ -402,15 +275,13 @@ __device__ __forceinline__ void mesh_stage_apron10(const FrameParams &fp, const 
 }
 
 // bit o (o = dx | dy << 1 | dz << 2): the block at key - (dx, dy, dz) lies in the region
-__device__ __forceinline__ uint32_t mesh_region_bits(const int4 &item, const MeshRegion &rg)
+__device__ __forceinline__ uint32_t mesh_region_bits(const int4 &item, const BlockBox &rg)
 {
     uint32_t bits = 0;
 #pragma unroll
     for (int o = 0; o < 8; ++o) {
         // (|key| < 2^28: the subtraction cannot wrap)
-        const int kx = item.x - (o & 1), ky = item.y - ((o >> 1) & 1), kz = item.z - (o >> 2);
-        const bool in = kx >= rg.lo[0] && kx < rg.hi[0] && ky >= rg.lo[1] && ky < rg.hi[1] && kz >= rg.lo[2] && kz < rg.hi[2];
-        bits |= (in ? 1u : 0u) << o;
+        bits |= (rg.holds(item.x - (o & 1), item.y - ((o >> 1) & 1), item.z - (o >> 2)) ? 1u : 0u) << o;
     }
     return bits;
 }
@@ -437,7 +308,7 @@ __device__ __forceinline__ uint32_t mesh_voxel_edges(const MeshApron10 &ap, cons
 
 // One listed block (of the grown region) per workgroup pass, two x-neighbouring voxels per lane.  word[b * 512 + voxel] =
 // prefix of the block's vertices before the voxel << 7 | mask; vertexCount[b], triangleCount[b] (0 outside the region).
-__global__ __launch_bounds__(256) void mesh_indexed_count_kernel(const FrameParams fp, const DevPtrs dp, const MeshRegion rg,
+__global__ __launch_bounds__(256) void mesh_indexed_count_kernel(const FrameParams fp, const DevPtrs dp, const BlockBox rg,
                                                                  const int4 *__restrict__ items,
                                                                  const unsigned long long *__restrict__ numItems, uint32_t listCapacity,
                                                                  uint32_t *__restrict__ listPos, uint32_t listPosSize,
@@ -473,7 +344,7 @@ __global__ __launch_bounds__(256) void mesh_indexed_count_kernel(const FramePara
         if (inRegion & 1u) tris = mesh_cell_count(mesh_cell_mask(ap, x, y, z)) + mesh_cell_count(mesh_cell_mask(ap, x + 1, y, z));
         // one scan for both: a block has at most 3 584 vertices and 6 144 triangles, 16 bits each
         uint32_t total;
-        const uint32_t before = mesh_wg_scan((v0 + v1) | (tris << 16), sWave, total) & 0xffffu;   // (its barriers fence the LDS for the next pass)
+        const uint32_t before = block_wg_scan((v0 + v1) | (tris << 16), sWave, total) & 0xffffu;   // (its barriers fence the LDS for the next pass)
         *reinterpret_cast<uint2 *>(word + (size_t)b * 512u + 2 * tid) = make_uint2((before << 7) | e0, ((before + v0) << 7) | e1);
         if (tid == 0) {
             vertexCount[b] = total & 0xffffu;
@@ -495,7 +366,7 @@ __device__ __forceinline__ uint32_t mesh_vertex_index(uint32_t base, uint32_t w,
 // word of A, in this block (LDS) or in one of the seven +neighbours (their list position through listPos).
 // result = {listed blocks, vertices, triangles}: nothing is written when the vertices do not fit 32 bits.
 template <bool kNormals>
-__global__ __launch_bounds__(256) void mesh_indexed_emit_kernel(const FrameParams fp, const DevPtrs dp, const MeshRegion rg,
+__global__ __launch_bounds__(256) void mesh_indexed_emit_kernel(const FrameParams fp, const DevPtrs dp, const BlockBox rg,
                                                                 const int4 *__restrict__ items,
                                                                 const unsigned long long *__restrict__ result, uint32_t listCapacity,
                                                                 const uint32_t *__restrict__ listPos, uint32_t listPosSize,
@@ -530,7 +401,7 @@ __global__ __launch_bounds__(256) void mesh_indexed_emit_kernel(const FrameParam
             uint32_t pos = 0, base = 0;
             if (p != VH_FREE_BLOCK && ((uint32_t)p >> 9) < listPosSize) {
                 pos = listPos[(uint32_t)p >> 9];
-                if (pos < count) base = (uint32_t)(vertexTiles[pos / (uint32_t)kMeshScanTile] + vertexOffset[pos]);
+                if (pos < count) base = (uint32_t)scanned_at(vertexTiles, vertexOffset, pos);
                 else pos = 0;
             }
             sPos[tid] = pos;
@@ -564,8 +435,8 @@ __global__ __launch_bounds__(256) void mesh_indexed_emit_kernel(const FrameParam
             const uint32_t m[2] = {mesh_cell_mask(ap, x, y, z), mesh_cell_mask(ap, x + 1, y, z)};
             const uint32_t c[2] = {mesh_cell_count(m[0]), mesh_cell_count(m[1])};
             uint32_t total;
-            const uint32_t before = mesh_wg_scan(c[0] + c[1], sWave, total);
-            unsigned long long at = triangleTiles[b / (uint32_t)kMeshScanTile] + triangleOffset[b] + before;
+            const uint32_t before = block_wg_scan(c[0] + c[1], sWave, total);
+            unsigned long long at = scanned_at(triangleTiles, triangleOffset, b) + before;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 if (!c[h]) continue;

@@ -1,9 +1,8 @@
 // vh_stream.hip -- block streaming between the model and caller memory: vh_stream_out / vh_stream_in (DESIGN.md 4.16;
 // include/voxelhash.h states the rule, tests/stream_ref.py is its executable form; Niessner et al. 2013, section 5; no counterpart
-// in the reference).  Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after everything else: the scans are
-// vh_mesh.hip's, the lookup vh_merge.hip's, the marks and the deletion vh_gc.hip's, the insertion vh_shard.hip's and vh_alloc.hip's.
-//   stream_list_kernel<false>  vh_mesh.hip's list walk with the streaming region as predicate: allocated entries inside counted
-//   stream_list_kernel<true>   the same walk, entries written in ascending entry index as {x, y, z, ptr}
+// in the reference).  Part of libvoxelhash_hip.so (gfx950); included by vh_kernels.hip after everything else: the list and its
+// scans are vh_blocklist.hip's, the lookup vh_merge.hip's, the marks and the deletion vh_gc.hip's, the insertion vh_shard.hip's and vh_alloc.hip's.
+//   (vh_blocklist.hip          the ordered block list with the streaming region, a StreamSelect, as predicate)
 //   stream_pack_kernel         one workgroup pass per listed block: key + 4 KiB of voxels into a vh_view_record, 16 bytes per lane
 //                              (view_pack_kernel's copy), and the 2 KiB of colour words, 8 bytes per lane
 //   stream_classify_kernel     one lane per incoming record: FOREIGN, PRESENT, or a record of the key bin the allocation rounds take
@@ -13,80 +12,38 @@
 
 namespace vh {
 
-// vh_stream_region as the kernels take it: radius2 = radius * radius, rounded once on the host
-struct StreamRegion {
-    int kind, invert;
-    int lo[3], hi[3];
-    float centre[3], radius2;
-};
 constexpr int kStreamBox = 0, kStreamSphere = 1;               // VH_STREAM_BOX / VH_STREAM_SPHERE
 constexpr int kStreamPending = -1;                             // a record the classification left for the rounds
 constexpr int kStreamRecordBytes = 4112;                       // sizeof(vh_view_record)
 
+// vh_stream_region as the list walk takes it, its predicate: radius2 = radius * radius, rounded once on the host
+struct StreamSelect {
+    int kind, invert;
+    BlockBox box;
+    float centre[3], radius2, voxelSize;
+    __device__ __forceinline__ bool operator()(const VoxelEntry &e) const;
+};
+
 // The selection rule, float32, every operation rounded on its own (the file is built without contraction)
-__device__ __forceinline__ bool stream_selected(const int *pos, const StreamRegion &rg, float voxelSize)
+__device__ __forceinline__ bool stream_selected(const int *pos, const StreamSelect &rg)
 {
     bool inside;
     if (rg.kind == kStreamBox) {
-        inside = pos[0] >= rg.lo[0] && pos[0] < rg.hi[0] && pos[1] >= rg.lo[1] && pos[1] < rg.hi[1] && pos[2] >= rg.lo[2] &&
-                 pos[2] < rg.hi[2];
+        inside = rg.box.holds(pos[0], pos[1], pos[2]);
     } else {
         // (8 * key in wrapping 32-bit arithmetic, as block_in_frustum has it: exact inside the key domain)
-        const float x0 = ((float)(int)((uint32_t)pos[0] * 8u) + 3.5f) * voxelSize - rg.centre[0];
-        const float x1 = ((float)(int)((uint32_t)pos[1] * 8u) + 3.5f) * voxelSize - rg.centre[1];
-        const float x2 = ((float)(int)((uint32_t)pos[2] * 8u) + 3.5f) * voxelSize - rg.centre[2];
+        const float x0 = ((float)(int)((uint32_t)pos[0] * 8u) + 3.5f) * rg.voxelSize - rg.centre[0];
+        const float x1 = ((float)(int)((uint32_t)pos[1] * 8u) + 3.5f) * rg.voxelSize - rg.centre[1];
+        const float x2 = ((float)(int)((uint32_t)pos[2] * 8u) + 3.5f) * rg.voxelSize - rg.centre[2];
         const float d2 = (x0 * x0 + x1 * x1) + x2 * x2;
         inside = d2 <= rg.radius2;
     }
     return inside != (rg.invert != 0);
 }
 
-__device__ __forceinline__ bool stream_listed(const VoxelEntry &e, const StreamRegion &rg, float voxelSize)
+__device__ __forceinline__ bool StreamSelect::operator()(const VoxelEntry &e) const
 {
-    return e.ptr != VH_FREE_BLOCK && stream_selected(e.pos, rg, voxelSize);
-}
-
-// mesh_list_kernel (vh_mesh.hip) for this predicate: one lane per bucket, 64 consecutive buckets per round, every slot looked at
-// (with the overflow list an entry may sit anywhere), the lanes' counts put in lane order by a wave scan.
-// kWrite = false: sliceCount[wave] = listed entries of the wave's slice.  kWrite = true: they are written from
-// tileBase[wave / kMeshScanTile] + sliceCount[wave] (what the scan left there) on.
-template <bool kWrite>
-__global__ __launch_bounds__(256) void stream_list_kernel(const FrameParams fp, const DevPtrs dp, const StreamRegion rg,
-                                                          uint32_t ownedBuckets, uint32_t numSlices, uint32_t *sliceCount,
-                                                          const unsigned long long *__restrict__ tileBase, int4 *items,
-                                                          uint32_t capacity)
-{
-    const uint32_t lane = threadIdx.x & 63u, slice = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (slice >= numSlices) return;
-    uint32_t running = 0;
-    if (kWrite) running = (uint32_t)tileBase[slice / kMeshScanTile] + sliceCount[slice];
-    const uint32_t first = slice * (uint32_t)kMeshSliceBuckets;
-    for (uint32_t r = 0; r < (uint32_t)kMeshSliceBuckets; r += 64u) {
-        const uint32_t b = first + r + lane;
-        const bool occupied = b < ownedBuckets && ((dp.bucketBits[b >> 5] >> (b & 31u)) & 1u);
-        if (__ballot(occupied) == 0ull) continue;
-        const VoxelEntry *bucket = dp.table + (size_t)b * fp.bucketSize;
-        uint32_t n = 0;
-        if (occupied)
-            for (uint32_t s = 0; s < fp.bucketSize; ++s) n += stream_listed(bucket[s], rg, fp.voxelSize) ? 1u : 0u;
-        uint32_t incl = n;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if ((int)lane >= d) incl += up;
-        }
-        if (kWrite && n) {
-            uint32_t at = running + incl - n;
-            for (uint32_t s = 0; s < fp.bucketSize; ++s) {
-                const VoxelEntry e = bucket[s];
-                if (!stream_listed(e, rg, fp.voxelSize)) continue;
-                if (at < capacity) items[at] = make_int4(e.pos[0], e.pos[1], e.pos[2], e.ptr);
-                ++at;
-            }
-        }
-        running += __shfl(incl, 63);
-    }
-    if (!kWrite && lane == 0) sliceCount[slice] = running;
+    return e.ptr != VH_FREE_BLOCK && stream_selected(e.pos, *this);
 }
 
 // Record b <- listed block b, b < count (the host has read the list's length): lane t copies voxels 2t, 2t + 1 as one 16-byte
