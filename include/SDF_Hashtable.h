@@ -160,6 +160,18 @@ public:
     uint64_t streamOut(const vh_stream_region &region, std::vector<vh_view_record> &records, std::vector<uint32_t> *colors = nullptr);
     void streamIn(const std::vector<vh_view_record> &records, const std::vector<uint32_t> *colors = nullptr,
                   std::vector<int32_t> *status = nullptr, vh_stream_stats *stats = nullptr);
+    /* Incremental meshing (vh_changes_host / vh_extract_mesh_blocks_host, voxelhash.h "incremental meshing").  d_state: a DEVICE
+     * buffer of changesStateBytes() bytes the caller owns, all zero at first.  changedBlocks lists the blocks of `region`
+     * (nullptr: the whole model) that differ from what the state last saw -- changed: 4 int32 per block {x, y, z, flags =
+     * VH_CHANGED_SELF | VH_CHANGED_HALO}, in entry order; removed: {x, y, z, 0} -- and advances the state; returns the number
+     * of changed blocks.  extractMeshBlocks gives the triangles of a key list (4 int32 per key, the 4th ignored: `changed` as
+     * it is): positions = 9 floats per triangle, first = keys + 1 offsets (key j's triangles are first[j] .. first[j + 1]),
+     * normals optional; returns the triangle count.  Both synchronise. */
+    uint64_t changesStateBytes();
+    uint64_t changedBlocks(void *d_state, std::vector<int32_t> &changed, std::vector<int32_t> &removed,
+                           const vh_mesh_region *region = nullptr, int what = VH_CHANGES_VOXELS, int halo = VH_CHANGES_HALO_MESH);
+    uint64_t extractMeshBlocks(const std::vector<int32_t> &keys, std::vector<float> &positions, std::vector<uint64_t> &first,
+                               std::vector<float> *normals = nullptr);
     void registerGLtoCUDA(SDFRenderer &) {}
     void unmapCUDApointers() {}
 

@@ -1237,6 +1237,92 @@ int vh_remove_components(vh_context *ctx, const vh_mesh_region *region, int32_t 
                          uint64_t min_size, vh_component_stats *stats /* host, may be NULL */);
 
 /* ------------------------------------------------------------------ */
+/* incremental meshing: which blocks changed, and their triangles      */
+/* (tests/changes_ref.py is the rule in executable form) */
+/* ------------------------------------------------------------------ */
+/* A live consumer of the model (a viewer, a remote client, a planner's map) keeps a mesh chunk per block and re-meshes only
+ * the blocks a frame, a merge, a de-integration, a collection, a streaming call or a component removal touched.  No
+ * model-changing call records what it touched: vh_changes finds out afterwards, by comparing a digest of every allocated
+ * block's bits with a small STATE the caller keeps, so one streaming read of the allocated blocks serves every call that
+ * changes the model, whichever and however many ran since the state last advanced.
+ *
+ * State.  A device buffer the caller owns, vh_changes_state_bytes() bytes (64 + 32 per block of the pool); all-zero bytes
+ * is the empty state (nothing seen yet).  Layout (part of this specification): a 64-byte header whose first uint64 is the
+ * EPOCH, the number of calls that advanced the state, the rest zero; then one 32-byte slot per pool block, indexed by the
+ * block's ptr >> 9: {int32 key[3]; uint32 live; uint64 h0; uint64 h1}.  An empty slot is all zero.  One state serves one
+ * `what` and one context.
+ *
+ * Digest of a block, in wrapping uint64 arithmetic.  For voxel i = 0..511: x_i = (uint64)bits(weight) << 32 | bits(sdf).
+ *     mix(z):  z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31   (splitmix64)
+ *     G = 0x9e3779b97f4a7c15;   m_i = mix(x_i + (i + 1) * G + what);   h0 = sum m_i;   h1 = sum m_i * (2 i + 1)
+ * With VH_CHANGES_COLOR the colour word c_i of every voxel (0 while the context has no colour volume) adds a term:
+ *     m'_i = mix(c_i + (i + 513) * G + what), added to h0, and m'_i * (2 (i + 512) + 1), added to h1.
+ * Bits are compared: -0.0 against +0.0 and two NaN payloads differ.  What the digest guarantees: mix is a bijection, so a
+ * change confined to ONE voxel's {sdf, weight} pair, or to ONE colour word, of a block is ALWAYS detected.  Its limit: any
+ * other change of a block goes unnoticed only if both 64-bit sums collide, heuristically with a probability of the order
+ * of 2^-64 or less per block and comparison; the digest is NOT cryptographic, and bits chosen by an adversary can collide.
+ *
+ * Rule.  The allocated blocks of the region grown by one block on every side (saturating at the ends of int32) are listed
+ * in ascending entry index of the hash table (the mesh's block list).
+ *   A listed block INSIDE the region, key K, pool slot p = ptr >> 9, is SELF-CHANGED iff state slot p is not live, holds
+ *     another key, or holds another digest.
+ *   A live state slot whose key lies inside the region is STALE iff no listed block of this call has that slot and key.
+ *   A stale slot's key is REMOVED iff the table holds no entry with that key now (the bucket probe, overflow list
+ *     included).  A key that came back under another pool slot is not removed: it is self-changed at its new slot.
+ *   Halo.  For every self-changed or removed key k the allocated blocks k + o, o != 0, are listed with the halo flag:
+ *     VH_CHANGES_HALO_NONE none; VH_CHANGES_HALO_MESH o in {-1, 0}^3 (the cells of block j read the blocks j + {0, 1}^3:
+ *     what vh_extract_mesh_blocks without normals depends on); VH_CHANGES_HALO_NORMALS o in {-1, 0, 1}^3 (the gradient at
+ *     an apron voxel reaches one voxel further both ways: with normals).  Halo blocks one block outside the region are
+ *     listed too.
+ *   d_changed: 4 int32 per block, {x, y, z, flags}, flags = VH_CHANGED_SELF | VH_CHANGED_HALO (a block can carry both), in
+ *     ascending entry index.  d_removed: {x, y, z, 0} in ascending state slot.  Both orders are reproducible.
+ *   Commit, all or nothing, decided on the device: iff BOTH counts fit their capacities the lists are written and the state
+ *     advances -- the slots of the self-changed blocks are written, the stale slots emptied, the epoch counted up (also
+ *     when nothing changed).  Otherwise the counts are reported (VH_OK), nothing is written to the lists, the state is byte
+ *     for byte what it was, and the caller calls again with larger buffers.  So capacity 0 with NULL buffers is a PEEK that
+ *     consumes changes only when there are none.  Changes outside the region stay pending for a later call.
+ * The call runs on the context's stream behind every frame queued so far (a pending pipelined frame is launched first),
+ * reads the two counts back in one copy, synchronises once, and changes nothing in the model.  It works on shards (a block
+ * of another shard is absent: never halo, never keeping a key from being removed) and with "overflow_list".  View tables
+ * are refused with VH_ERR_INVALID_ARGUMENT: they are rebuilt by import, not edited.  VH_ERR_INVALID_ARGUMENT also for a
+ * NULL state or count, a `what` without VH_CHANGES_VOXELS or with unknown bits, an unknown halo, a capacity without its
+ * buffer.  Scratch beyond the block list's (a flag word and two digest words per listed block, three words per pool block)
+ * is allocated at the first call and kept; a context that never calls this allocates nothing for it.  vh_changes_host
+ * takes host lists (the state stays a device buffer). */
+#define VH_CHANGES_VOXELS 1
+#define VH_CHANGES_COLOR  2
+#define VH_CHANGES_HALO_NONE    0
+#define VH_CHANGES_HALO_MESH    1
+#define VH_CHANGES_HALO_NORMALS 2
+#define VH_CHANGED_SELF 1
+#define VH_CHANGED_HALO 2
+int vh_changes_state_bytes(vh_context *ctx, uint64_t *bytes);
+int vh_changes(vh_context *ctx, void *d_state, const vh_mesh_region *region /* NULL: whole model */,
+               int32_t what /* VH_CHANGES_VOXELS [| VH_CHANGES_COLOR] */, int32_t halo /* VH_CHANGES_HALO_* */,
+               uint64_t capacity_changed, int32_t *d_changed /* 4 per block: x, y, z, flags */,
+               uint64_t capacity_removed, int32_t *d_removed /* 4 per block: x, y, z, 0 */,
+               uint64_t *changed_out, uint64_t *removed_out /* host */);
+int vh_changes_host(vh_context *ctx, void *d_state, const vh_mesh_region *region, int32_t what, int32_t halo,
+                    uint64_t capacity_changed, int32_t *h_changed, uint64_t capacity_removed, int32_t *h_removed,
+                    uint64_t *changed_out, uint64_t *removed_out);
+
+/* The triangles of a LIST of blocks, block by block.  d_keys: n keys, 4 int32 each, the 4th ignored (vh_changes' d_changed
+ * feeds it directly).  For key j of the list the call writes the triangles of the cells block j owns: exactly the bytes
+ * vh_extract_mesh writes for the region [j, j + 1), positions and normals, at triangles d_first[j] .. d_first[j + 1] of the
+ * buffers, in the list's order.  An absent key has an empty range; a key that occurs twice gets its copy each time.
+ * d_first (n + 1 uint64 on the device, or NULL) always holds the unclipped offsets; clipping at the capacity, the count-only
+ * call and *triangles_out are as in vh_extract_mesh.  n == 0 returns VH_OK with 0 triangles and launches nothing; n above
+ * the number of blocks the table can hold (numVoxelBlocks; the imported records of a view table) is
+ * VH_ERR_INVALID_ARGUMENT.  Stream order, the one synchronisation, shards, view tables and "mesh_variant" as for
+ * vh_extract_mesh.  There is no per-block indexed form (vertex ownership crosses blocks); per-vertex colour is
+ * vh_sample_color over the positions. */
+int vh_extract_mesh_blocks(vh_context *ctx, uint64_t n, const int32_t *d_keys /* 4 per block; the 4th is ignored */,
+                           uint64_t capacity_triangles, float *d_positions, float *d_normals /* or NULL */,
+                           uint64_t *d_first /* n + 1 offsets, device, or NULL */, uint64_t *triangles_out);
+int vh_extract_mesh_blocks_host(vh_context *ctx, uint64_t n, const int32_t *h_keys, uint64_t capacity_triangles,
+                                float *h_positions, float *h_normals, uint64_t *h_first, uint64_t *triangles_out);
+
+/* ------------------------------------------------------------------ */
 /* model dump / checkpoint                     */
 /* ------------------------------------------------------------------ */
 /* Text dump in the format of SDFRenderer::printSDFdata (SDFRenderer.cpp:71-110, written to

@@ -18,8 +18,11 @@ box of the model's blocks, up to --esdf-radius voxels (default 16), unknown voxe
 --min-component N takes the floaters out before --mesh, --mesh-indexed, --esdf and --snapshot: every inside component (at
 connectivity 14, the mesh's own) with fewer than N voxels is cleared out of the volume and the blocks that emptied are freed
 (vh_remove_components); the stats are printed.
-tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--color] [--tracker icp|sdf-color]
-                       [--snapshot out.vhsnap] [--stream-radius R]
+--mesh-live out.ply keeps a meshing.MeshCache across the run: after every frame (and whatever collected, streamed or removed
+blocks) one update() re-meshes only the blocks vh_changes lists (vh_extract_mesh_blocks); its final state is written, three
+vertices per triangle with normals, blocks in ascending key order.
+tools/pipeline_demo.py [frames] [--mesh out.ply] [--mesh-indexed out.ply] [--mesh-live out.ply] [--color]
+                       [--tracker icp|sdf-color] [--snapshot out.vhsnap] [--stream-radius R]
                        [--esdf out.npy] [--esdf-radius R] [--min-component N]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,6 +37,10 @@ MESH = MESH_INDEXED = None
 if "--mesh-indexed" in argv:
     MESH_INDEXED = argv[argv.index("--mesh-indexed") + 1]
     del argv[argv.index("--mesh-indexed"):argv.index("--mesh-indexed") + 2]
+MESH_LIVE = None
+if "--mesh-live" in argv:
+    MESH_LIVE = argv[argv.index("--mesh-live") + 1]
+    del argv[argv.index("--mesh-live"):argv.index("--mesh-live") + 2]
 if "--mesh" in argv:
     MESH = argv[argv.index("--mesh") + 1]
     del argv[argv.index("--mesh"):argv.index("--mesh") + 2]
@@ -88,6 +95,13 @@ if STREAM_RADIUS is not None:
     store = streaming.BlockStore(table.params.voxelSize)
     stage["stream"] = 0.0
     streamed = dict(out=0, back=0, most=0)
+cache = None
+if MESH_LIVE:
+    from voxelhashing_demo_amd import meshing
+    with torch.cuda.stream(stream):
+        cache = meshing.MeshCache(table, normals=True)
+    stage["mesh_live"] = 0.0
+    live = dict(extracted=0, removed=0, allocated=0)
 if COLOR:
     stage["color"] = 0.0
     BAND = 3.0 * table.params.voxelSize
@@ -146,6 +160,12 @@ with torch.cuda.stream(stream):
             streamed["out"] += moved[0]["out"]
             streamed["back"] += moved[0]["in"]
             streamed["most"] = max(streamed["most"], moved[0]["stored"])
+        if cache is not None:
+            did = [None]
+            timed("mesh_live", lambda: did.__setitem__(0, cache.update()))
+            live["extracted"] += did[0]["extracted"]
+            live["removed"] += did[0]["removed"]
+            live["allocated"] += len(cache.blocks)
         errs.append(float(np.abs(pose[:3, 3] - np.asarray(gt[k], np.float64).reshape(4, 4)[:3, 3]).max()))
 travel = float(np.linalg.norm(np.asarray(gt[-1], np.float64).reshape(4, 4)[:3, 3] - np.asarray(gt[0], np.float64).reshape(4, 4)[:3, 3]))
 print(f"{N} frames, {travel:.2f} m between first and last camera, blocks {table.counters()['allocated_total']}")
@@ -167,6 +187,15 @@ if MIN_COMPONENT:
     print(f"components: blocks={removed['blocks']} inside voxels={removed['nodes']} components={removed['components']} "
           f"largest={removed['largest']}; below {MIN_COMPONENT} voxels: {removed['removed_components']} components, "
           f"{removed['removed_voxels']} voxels removed, {removed['freed_blocks']} blocks freed ({1e3 * dt:.1f} ms)")
+if MESH_LIVE:
+    from voxelhashing_demo_amd import mesh_io
+    with torch.cuda.stream(stream):
+        last = cache.update()                     # what the restore and the component removal above changed
+    lp, ln = cache.triangles()
+    mesh_io.save_ply(MESH_LIVE, lp.reshape(-1, 3), np.arange(3 * len(lp), dtype=np.int32).reshape(-1, 3), ln.reshape(-1, 3))
+    print(f"mesh live: triangles={len(lp)} in {len(cache.blocks)} blocks; {live['extracted']} block extractions over {N} updates "
+          f"where re-meshing every block each time would be {live['allocated']}, {live['removed']} blocks dropped; the last "
+          f"update re-meshed {last['extracted']} -> {MESH_LIVE}")
 if MESH:
     from voxelhashing_demo_amd import mesh_io
     with torch.cuda.stream(stream):

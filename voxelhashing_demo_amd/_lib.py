@@ -25,6 +25,10 @@ ESDF_FAR, ESDF_NONE = 2**31 - 1, -2**31            # d_dist2: nothing of the oth
 RAY_HIT, RAY_MISS, RAY_REFUSED = 1, 0, -1          # the status word of vh_cast_rays' d_voxels
 COMPONENT_INSIDE, COMPONENT_OUTSIDE, COMPONENT_NONE = 0, 1, 0xFFFFFFFF      # vh_components: target; the label of a voxel that is no node
 STREAM_BOX, STREAM_SPHERE = 0, 1                   # vh_stream_region.kind
+CHANGES_VOXELS, CHANGES_COLOR = 1, 2               # vh_changes: what the digest covers
+CHANGES_HALO_NONE, CHANGES_HALO_MESH, CHANGES_HALO_NORMALS = 0, 1, 2       # ... and which neighbours of a changed block are listed
+CHANGED_SELF, CHANGED_HALO = 1, 2                  # the flags word of vh_changes' d_changed
+CHANGES_HEADER_BYTES, CHANGES_SLOT_BYTES = 64, 32  # the state: a header (first word the epoch), a slot per pool block
 STREAM_PLACED, STREAM_PRESENT, STREAM_UNPLACED, STREAM_FOREIGN = 0, 1, 2, 3       # the per-record status of vh_stream_in
 
 
@@ -217,6 +221,13 @@ SIGNATURES = {
     "vh_components_host": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, _vp, C.POINTER(_i32), C.POINTER(_i32), _vp,
                                      C.POINTER(ComponentStats)]),
     "vh_remove_components": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, C.POINTER(ComponentStats)]),
+    "vh_changes_state_bytes": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "vh_changes": (C.c_int, [_vp, _vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64),
+                             C.POINTER(C.c_uint64)]),
+    "vh_changes_host": (C.c_int, [_vp, _vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, _vp, C.c_uint64, _vp,
+                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vh_extract_mesh_blocks": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "vh_extract_mesh_blocks_host": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "vh_sdf_build_system": (C.c_int, [_vp, _vp, _vp, _fp, _f, C.POINTER(IcpSystem)]),
     "vh_sdf_residuals": (C.c_int, [_vp, _vp, _vp, _fp, _f, _vp, _vp, _vp, C.POINTER(IcpSystem)]),
     "vh_sdf_align": (C.c_int, [_vp, _vp, _vp, _f, C.c_int32, C.POINTER(C.c_double), C.POINTER(IcpSystem), C.POINTER(C.c_int32)]),

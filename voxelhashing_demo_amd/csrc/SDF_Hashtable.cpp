@@ -301,6 +301,46 @@ void SDF_Hashtable::streamIn(const std::vector<vh_view_record> &records, const s
                             stats), "streamIn");
 }
 
+uint64_t SDF_Hashtable::changesStateBytes()
+{
+    uint64_t bytes = 0;
+    check(vh_changes_state_bytes(ctx_, &bytes), "changesStateBytes");
+    return bytes;
+}
+
+uint64_t SDF_Hashtable::changedBlocks(void *d_state, std::vector<int32_t> &changed, std::vector<int32_t> &removed,
+                                      const vh_mesh_region *region, int what, int halo)
+{
+    // a peek for the counts (it advances the state only when there is nothing to list), then the call that takes them
+    uint64_t nc = 0, nr = 0;
+    check(vh_changes_host(ctx_, d_state, region, what, halo, 0, nullptr, 0, nullptr, &nc, &nr), "changedBlocks");
+    changed.assign((size_t)nc * 4, 0);
+    removed.assign((size_t)nr * 4, 0);
+    if (nc || nr)
+        check(vh_changes_host(ctx_, d_state, region, what, halo, nc, nc ? changed.data() : nullptr, nr, nr ? removed.data() : nullptr,
+                              &nc, &nr), "changedBlocks");
+    if (changed.size() != (size_t)nc * 4 || removed.size() != (size_t)nr * 4) {
+        std::fprintf(stderr, "SDF_Hashtable: the model changed between the two calls of changedBlocks\n");
+        std::exit(EXIT_FAILURE);
+    }
+    return nc;
+}
+
+uint64_t SDF_Hashtable::extractMeshBlocks(const std::vector<int32_t> &keys, std::vector<float> &positions, std::vector<uint64_t> &first,
+                                          std::vector<float> *normals)
+{
+    const uint64_t n = keys.size() / 4;
+    uint64_t count = 0, got = 0;
+    first.assign((size_t)n + 1, 0);
+    check(vh_extract_mesh_blocks_host(ctx_, n, keys.data(), 0, nullptr, nullptr, first.data(), &count), "extractMeshBlocks");
+    positions.assign((size_t)count * 9, 0.0f);
+    if (normals) normals->assign((size_t)count * 9, 0.0f);
+    if (count)
+        check(vh_extract_mesh_blocks_host(ctx_, n, keys.data(), count, positions.data(), normals ? normals->data() : nullptr,
+                                          first.data(), &got), "extractMeshBlocks");
+    return count;
+}
+
 uint64_t SDF_Hashtable::saveMeshPlyIndexed(const char *path, bool withNormals)
 {
     std::vector<float> pos, nrm;

@@ -173,6 +173,16 @@ struct ComponentScratch {
     DevBuf<int4> keys;                     // vh_remove_components: the keys of the blocks that emptied
 };
 
+// vh_changes, vh_extract_mesh_blocks (vh_api_changes.hip names the parts): scratch of the first call of each, kept
+struct ChangesScratch {
+    DevBuf<uint32_t> words;                // vh_changes: a flag word per listed block, then per pool block listPos[ptr >> 9], the slot flags, the removed counts
+    DevBuf<unsigned long long> wide;       // ... two digest words per listed block, the removed scan's tile totals, then {listed, changed, removed}
+    DevBuf<uint32_t> keyWords;             // vh_extract_mesh_blocks: per key its block's ptr, then its place among the present keys
+    DevBuf<unsigned long long> keyTiles;   // ... and that scan's tile totals
+    DevBuf<int32_t> hostKeys;              // the _host forms: the lists in device memory
+    DevBuf<unsigned long long> hostFirst;
+};
+
 struct vh_context {
     HashTableParams params;
     FrameParams fp;
@@ -263,6 +273,7 @@ struct vh_context {
     DevBuf<uint32_t> color;                // the colour volume (vh_api_color.hip): one word per voxel, of the first colour-fusing call, kept
     StreamScratch streaming;               // vh_stream_in, vh_stream_*_host: scratch of the first call, kept
     ComponentScratch components;           // vh_components, vh_remove_components: scratch of the first call, kept
+    ChangesScratch changes;                // vh_changes, vh_extract_mesh_blocks: scratch of the first call, kept
 };
 
 // a scratch buffer (a DevBuf the context keeps) of at least `count` elements; what still uses a smaller one is synchronised away first
@@ -651,3 +662,4 @@ static int ensure_band_candidates(vh_context *c)
 #include "vh_api_dist.hip"
 #include "vh_api_stream.hip"
 #include "vh_api_components.hip"
+#include "vh_api_changes.hip"

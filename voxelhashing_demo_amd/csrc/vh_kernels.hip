@@ -44,6 +44,9 @@
 //   vh_components.hip  connected pieces of the model: a union-find over the sparse blocks (in LDS inside a block, atomicMin on the
 //                      larger root across the seams), sizes, records and labels in root order, removal of the small pieces
 //                      through the deletion path (no counterpart in the reference)
+//   vh_changes.hip     incremental meshing: a digest per block against a caller-kept state says which blocks changed, were removed
+//                      or read a changed neighbour; a list of keys in front of the mesh's per-block kernel (no counterpart in
+//                      the reference)
 //   vh_preprocess.hip  depth -> vertex / normal maps (preProcess, CameraTrackingUtils.cu:50-120),
 //                      table set-up kernels (VoxelUtils.cu:151-166), device-side test hook
 //   vh_icp.hip         frame-to-frame point-to-plane ICP: correspondences + Jacobian + J^T J / J^T r in one
@@ -75,3 +78,4 @@
 #include "vh_color.hip"
 #include "vh_stream.hip"
 #include "vh_components.hip"
+#include "vh_changes.hip"

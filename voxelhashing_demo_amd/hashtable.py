@@ -565,6 +565,92 @@ class SDFHashtable:
             out += (np.where(tri != 0, tri, near),)
         return out
 
+    # ---- incremental meshing ----
+    _CHANGES_HALOS = {"none": L.CHANGES_HALO_NONE, "mesh": L.CHANGES_HALO_MESH, "normals": L.CHANGES_HALO_NORMALS}
+    CHANGES_SLOT_DTYPE = np.dtype([("key", "<i4", (3,)), ("live", "<u4"), ("h0", "<u8"), ("h1", "<u8")])      # a slot of the state
+
+    def changes_state_bytes(self) -> int:
+        n = C.c_uint64()
+        L.check(self._lib.vh_changes_state_bytes(self._h, C.byref(n)), "vh_changes_state_bytes")
+        return int(n.value)
+
+    def changes_state(self):
+        """The empty state of vh_changes for this table: a zeroed CUDA tensor of uint8 (64 bytes of header, the first word the
+        epoch, then 32 bytes per pool block).  The caller keeps it between calls of changes()."""
+        import torch
+        with torch.cuda.device(self.device_index()):
+            return torch.zeros((self.changes_state_bytes(),), dtype=torch.uint8, device="cuda")
+
+    def changes_into(self, state, capacity_changed: int, changed, capacity_removed: int, removed, region=None, color: bool = False,
+                     halo="mesh"):
+        """vh_changes into caller-owned device buffers: changed int32 [capacity_changed, 4] = {x, y, z, flags}, removed int32
+        [capacity_removed, 4] (None with a capacity of 0).  Returns (changed, removed), the counts; the lists are written and
+        `state` advances only if both fit, so capacities of 0 peek.  Synchronises."""
+        what = L.CHANGES_VOXELS | (L.CHANGES_COLOR if color else 0)
+        mode = self._CHANGES_HALOS[halo] if isinstance(halo, str) else int(halo)
+        nc, nr = C.c_uint64(), C.c_uint64()
+        L.check(self._lib.vh_changes(self._h, _dev_ptr(state), self._mesh_region(region), what, mode, int(capacity_changed),
+                                     _dev_ptr(changed), int(capacity_removed), _dev_ptr(removed), C.byref(nc), C.byref(nr)),
+                "vh_changes")
+        return int(nc.value), int(nr.value)
+
+    def changes(self, state, region=None, color: bool = False, halo="mesh"):
+        """The blocks of `region` (None: the whole model) that differ from what `state` last saw, as CUDA tensors: (changed int32
+        [n, 4] = {x, y, z, flags} in the table's entry order, flags CHANGED_SELF | CHANGED_HALO; removed int32 [m, 4]).  halo
+        "mesh": also the blocks whose mesh reads a changed or removed block; "normals": ... whose mesh with normals does; "none".
+        color=True: the colour words count as well.  The state advances.  The buffers are kept on the table and grown, and the
+        call is made again, when a count does not fit: the tensors returned are views of them, valid until the next call."""
+        import torch
+        buf = getattr(self, "_changes_buffers", None)
+        if buf is None:
+            with torch.cuda.device(self.device_index()):
+                buf = self._changes_buffers = [torch.empty((64, 4), dtype=torch.int32, device="cuda"),
+                                               torch.empty((16, 4), dtype=torch.int32, device="cuda")]
+        while True:
+            nc, nr = self.changes_into(state, buf[0].shape[0], buf[0], buf[1].shape[0], buf[1], region, color, halo)
+            if nc <= buf[0].shape[0] and nr <= buf[1].shape[0]:
+                return buf[0][:nc], buf[1][:nr]
+            with torch.cuda.device(self.device_index()):
+                if nc > buf[0].shape[0]:
+                    buf[0] = torch.empty((nc + nc // 2, 4), dtype=torch.int32, device="cuda")
+                if nr > buf[1].shape[0]:
+                    buf[1] = torch.empty((nr + nr // 2, 4), dtype=torch.int32, device="cuda")
+
+    def extract_mesh_blocks_into(self, keys, capacity: int, positions, normals=None, first=None, n: int = None) -> int:
+        """vh_extract_mesh_blocks into caller-owned device buffers: keys int32 [n, 4] (the 4th word is ignored), positions and
+        normals [capacity, 3, 3] float32 (None with capacity 0), first [n + 1] int64 / uint64 or None.  Returns the triangles
+        the keys' blocks hold, which may exceed `capacity`."""
+        n = int(keys.shape[0]) if n is None else int(n)
+        t = C.c_uint64()
+        L.check(self._lib.vh_extract_mesh_blocks(self._h, n, _dev_ptr(keys) if n else None, int(capacity), _dev_ptr(positions),
+                                                 _dev_ptr(normals), _dev_ptr(first), C.byref(t)), "vh_extract_mesh_blocks")
+        return int(t.value)
+
+    def extract_mesh_blocks(self, keys, normals: bool = False):
+        """The triangles of the blocks `keys` (int32 [n, 3 or 4], a CUDA tensor or anything numpy takes; changes()'s first result
+        as it is), block by block: (positions [T, 3, 3] float32, normals [T, 3, 3] or None, first uint64 [n + 1]) in host
+        memory.  Block j's triangles are positions[first[j]:first[j + 1]], the bytes of extract_mesh(region=(j, j + 1)); an
+        absent key has none."""
+        import torch
+        with torch.cuda.device(self.device_index()):
+            if not isinstance(keys, torch.Tensor):
+                k = np.asarray(keys, np.int32)
+                k = k.reshape(-1, k.shape[-1] if k.ndim > 1 else 3)
+                keys = torch.from_numpy(np.ascontiguousarray(k)).cuda()
+            if keys.shape[-1] == 3:
+                keys = torch.cat([keys, torch.zeros_like(keys[:, :1])], dim=1)
+            keys = keys.to(torch.int32).contiguous()
+            n = int(keys.shape[0])
+            first = torch.zeros((n + 1,), dtype=torch.int64, device="cuda")
+            count = self.extract_mesh_blocks_into(keys, 0, None, None, first) if n else 0
+            pos = torch.empty((count, 3, 3), dtype=torch.float32, device="cuda")
+            nrm = torch.empty((count, 3, 3), dtype=torch.float32, device="cuda") if normals else None
+        if count:
+            got = self.extract_mesh_blocks_into(keys, count, pos, nrm, first)
+            if got != count:
+                raise L.VoxelHashError(f"the model changed between the count ({count}) and the extraction ({got})")
+        return pos.cpu().numpy(), (nrm.cpu().numpy() if normals else None), first.cpu().numpy().view(np.uint64)
+
     # ---- the model as a distance field (DESIGN.md 4.9) ----
     def sample_sdf_into(self, points, sdf, weight=None, gradient=None, mode: int = L.SAMPLE_TRILINEAR, n: int = None):
         """vh_sample_sdf into caller-owned device buffers: points [n, 3] float32 (world metres), sdf [n], weight [n] or None,
