@@ -547,10 +547,20 @@ int vh_import_views(vh_context *view, const vh_view_record *d_records, int32_t n
  *     table (shard): the 512 voxels are zeroed, ptr/512 goes back on the heap
  *     (removeSingleBlockInHeap, :336-341), the entry is removed and the later entries of its
  *     bucket move down in order (a bucket's entries stay a prefix of its slots, which
- *     insertVoxelEntry :421-456 and every lookup rely on).  Absent keys are skipped.
+ *     insertVoxelEntry :421-456 and every lookup rely on).  Absent keys, keys of another shard
+ *     and repetitions of a key are skipped.
+ *     With the option "overflow_list" there is no compaction: a freed slot simply becomes free.
+ *     Two exceptions keep the chains whole.  A bucket's last slot heads its chain: when it is
+ *     deleted while the chain is not empty it is refilled with its first follower (pos, ptr and
+ *     the follower's link to the rest), so "last slot free" always means "no chain".  A chained
+ *     entry is unlinked from its predecessor (prev.offset = curr.offset, :594).  The resulting
+ *     table does not depend on the order of the keys.
  *   vh_garbage_collect: the same for every entry of the compact list (the blocks the last frame
  *     saw) whose voxels have max weight == 0, or min |sdf| over the voxels with weight > 0
- *     >= sdf_threshold.
+ *     >= sdf_threshold.  The max weight is floored at 0 and a NaN weight is no weight, so a block
+ *     none of whose voxels has weight > 0 goes whatever the threshold.  A NaN |sdf| is no sample;
+ *     a block with no sample has min = +inf.  A NaN threshold compares false: then only the
+ *     blocks without an observed voxel go.
  * Both leave the compact list empty (occupied = 0 until the next frame); vh_counters.last_freed
  * / freed_total report what was freed. */
 int vh_delete_blocks(vh_context *ctx, const int32_t *d_keys, int32_t n);

@@ -89,6 +89,44 @@ def snapshot_parts(empty, model, seed=0):
     return bytes(header), table, heap, payload
 
 
+ALLOCATED_TOTAL_AT = 208                           # uint32 allocatedTotal inside the header
+
+
+def snapshot_of_state(empty, table, heap, counter, voxels):
+    """The bytes of a VHSNAP01 file that holds an explicit state, slot for slot: `table` [entries] ENTRY (ptr, offset and the
+    pos of the free slots as given), `heap` [pool] uint32, the heap counter and `voxels` [pool * 512] VOXEL, from the bytes of
+    the snapshot an EMPTY context of the same parameters (and bucket range) saved.  heapCounter, allocatedTotal and
+    numAllocated of the header are patched."""
+    assert empty[:8] == b"VHSNAP01"
+    num_entries = int(np.frombuffer(empty, "<u8", 1, NUM_ALLOCATED_AT - 8)[0])
+    pool = int(np.frombuffer(empty, "<u4", 1, 8 + 128 + 12)[0])
+    assert len(empty) == HEADER_BYTES + num_entries * ENTRY.itemsize + pool * 4, "not the snapshot of an empty context"
+    table, heap = np.ascontiguousarray(table, ENTRY), np.ascontiguousarray(heap, "<u4")
+    voxels = np.ascontiguousarray(voxels, VOXEL).reshape(pool, 512)
+    assert len(table) == num_entries and len(heap) == pool
+    used = table["ptr"] != -1
+    assert int(used.sum()) + int(counter) + 1 == pool, "entries and free list do not partition the pool"
+    header = bytearray(empty[:HEADER_BYTES])
+    header[HEAP_COUNTER_AT:HEAP_COUNTER_AT + 4] = np.int32(counter).tobytes()
+    header[ALLOCATED_TOTAL_AT:ALLOCATED_TOTAL_AT + 4] = np.uint32(used.sum()).tobytes()
+    header[NUM_ALLOCATED_AT:NUM_ALLOCATED_AT + 8] = np.uint64(used.sum()).tobytes()
+    return bytes(header) + table.tobytes() + heap.tobytes() + voxels[table["ptr"][used] // 512].tobytes()
+
+
+def load_state(gt, table, heap, counter, voxels, tmp_path, name="state.snap"):
+    """Put an explicit state into the empty context `gt` through a snapshot (snapshot_of_state)."""
+    path = os.path.join(str(tmp_path), name)
+    gt.save_snapshot(path + ".empty")
+    with open(path + ".empty", "rb") as f:
+        empty = f.read()
+    os.remove(path + ".empty")
+    with open(path, "wb") as f:
+        f.write(snapshot_of_state(empty, table, heap, counter, voxels))
+    gt.load_snapshot(path)
+    os.remove(path)
+    return gt
+
+
 def write_snapshot(path, gt, model, seed=0):
     """A snapshot file gt.load_snapshot accepts, holding `model`.  `gt` must be empty: it saves itself for the header."""
     path = str(path)

@@ -66,7 +66,9 @@ __global__ __launch_bounds__(256) void gc_identify_kernel(const FrameParams fp, 
     for (int b = blockIdx.x; b < count; b += gridDim.x) {
         const VoxelEntry e = dp.compact[b];
         const float4 v = *reinterpret_cast<const float4 *>(dp.blocks + (size_t)e.ptr + 2 * threadIdx.x);
-        float mn = __builtin_inff(), mx = __builtin_fmaxf(v.y, v.w);
+        // (the max weight is floored at 0 as in the oracle: a block whose weights are all <= 0 or NaN has "max weight == 0",
+        // so it goes whatever the threshold, a NaN threshold included)
+        float mn = __builtin_inff(), mx = __builtin_fmaxf(0.0f, __builtin_fmaxf(v.y, v.w));
         if (v.y > 0.0f) mn = __builtin_fminf(mn, __builtin_fabsf(v.x));
         if (v.w > 0.0f) mn = __builtin_fminf(mn, __builtin_fabsf(v.z));
 #pragma unroll
