@@ -153,6 +153,20 @@ public:
                                const uint32_t *d_rgba, float band, int weightMax = 255);
     void saveColor(const char *path);
     void loadColor(const char *path);
+    /* The model with labels (voxelhash.h, the section of that name): d_labels = W*H uint16 labels registered to the depth image
+     * (0: not labelled), cast as one vote each into the voxels within `band` metres of the surface; voteMax 1..65535 caps a
+     * voxel's vote count, 0 only sweeps the labels of voxels that hold nothing.  Asynchronous. */
+    void integrateLabels(const float4x4 &pose, const uint16_t *d_depth, const float kInv[9], const uint16_t *d_labels, float band,
+                         int voteMax = 65535);
+    /* ... read back at world points through host buffers (vh_sample_labels_host): words = label | votes << 16 of the nearest
+     * voxel per point, 0 where there is no label or fewer than minVotes votes.  Synchronises. */
+    void sampleLabels(const std::vector<float> &points, std::vector<uint32_t> &words, int minVotes = 1);
+    /* ... counted (vh_label_counts_host): counts[l] = the valid voxels of `region` (nullptr: the whole model) with label l for
+     * 1 <= l < nBins, counts[0] = every other valid voxel.  Synchronises. */
+    void labelCounts(int nBins, std::vector<uint32_t> &counts, const vh_mesh_region *region = nullptr, int minVotes = 1);
+    /* ... and acted on (vh_remove_label): every voxel that carries `label` with at least minVotes votes cleared out of the
+     * volume, the blocks that emptied freed.  Returns the stats.  Synchronises. */
+    vh_label_stats removeLabel(int label, int minVotes = 1, const vh_mesh_region *region = nullptr);
     /* Block streaming (vh_stream_out_host / vh_stream_in_host, voxelhash.h "block streaming"): streamOut takes every allocated
      * block of `region` out of the model into `records` (key + 512 voxels each, in entry order) and, with `colors`, their 512
      * colour words each -- without it the colour of those blocks is dropped; returns the number of blocks moved.  streamIn puts

@@ -1247,6 +1247,100 @@ int vh_remove_components(vh_context *ctx, const vh_mesh_region *region, int32_t 
                          uint64_t min_size, vh_component_stats *stats /* host, may be NULL */);
 
 /* ------------------------------------------------------------------ */
+/* the model with labels                               */
+/* ------------------------------------------------------------------ */
+/* A per-pixel segmentation (the label image of a network, registered to the depth image) fused into the voxels near the
+ * surface, read back at points, at mesh vertices or per pixel of a raycast, counted per class, and acted on: everything that
+ * carries one label taken out of the volume.  tests/labels_ref.py is the rule in executable form; the reference has none.  The
+ * rule is all integers: the same model and images give the same words.  (The d_labels of vh_components holds component
+ * indices and has nothing to do with this section; "semantics" keeps meaning REFERENCE / PINHOLE.)
+ *   Voxel stays {sdf, weight}: labels live in a third volume of one uint32 per voxel, numVoxelBlocks * 512 words, the voxel at
+ *   volume index ptr + i having its word at ptr + i (the colour volume's layout).
+ *   Word: label | votes << 16, label 1..65535, votes 1..65535.  The word 0 means "no label".
+ *   The volume is allocated, zeroed, by the first label-fusing call into a context and kept.  A failed allocation returns
+ *   VH_ERR_OUT_OF_MEMORY and nothing changes.  A context that never fuses labels allocates nothing and behaves exactly as
+ *   before.  DevPtrs, Voxel, VoxelEntry, the snapshot format and vh_view_record are unchanged.
+ * FUSING.  d_labels is W*H uint16 values registered to the depth image; the value 0 marks a pixel the segmentation did not label.
+ *   Block set: vh_integrate_color's -- every allocated entry of this table (or shard) that passes blockInFrustum for `pose`,
+ *     the compact set of vh_set_pose(pose) + vh_flatten, chained overflow entries included.  No block is allocated or freed.
+ *   Per voxel of a listed block, with the stored voxel {os, ow} and its label word c = (l, n), l = c & 0xFFFF, n = c >> 16:
+ *     1. !(ow > 0): the word becomes 0 and nothing else happens to this voxel -- the sweep: a voxel that holds nothing has no
+ *        label, which also clears the labels a de-integration orphaned.
+ *     2. The camera point by the context's semantics, project, the image bounds test, the depth read, depth <= 0 rejects and
+ *        !(fabsf(depth - cz) <= band) rejects: all exactly as in vh_integrate_color.  A rejected voxel is untouched.
+ *     3. vote_max == 0, or the pixel's label L == 0: the voxel is untouched.
+ *     4. Otherwise one Boyer-Moore vote is cast:
+ *          n == 0            -> (L, 1)
+ *          l == L            -> (l, min(n + 1, vote_max))
+ *          l != L, n > 1     -> (l, n - 1)
+ *          l != L, n == 1    -> the word 0
+ *        Below the cap the stored label is a label that holds a strict majority of the votes cast, if there is one; vote_max
+ *        bounds how many opposing votes it takes to change a voxel's mind.
+ *   vh_integrate_labels reads the uint16 sensor image with vh_integrate_depth's arithmetic, vh_integrate_labels_map the .z of a
+ *   float4 vertex map.  Afterwards the context's pose is `pose`, the compact list and vh_counters.occupied are the flatten's;
+ *   the lock epoch, the heap, the hash table, the SDF volume and the colour volume are unchanged.  A pending pipelined frame is
+ *   launched first.  The calls only enqueue.  In vh_kernel_times the launch counts as integrate_ms, its flatten as flatten_ms.
+ *   Both semantics; with or without the overflow list; on shards every shard is called with the same arguments and labels its
+ *   own blocks.
+ *   VH_ERR_INVALID_ARGUMENT, with nothing changed: a NULL argument; band not finite or <= 0; vote_max outside 0..65535; a
+ *   context that holds an imported view.
+ * READING.  The domain, u = p / voxelSize, the nearest-voxel choice and voxel validity are those of vh_sample_sdf, mode
+ *   VH_SAMPLE_NEAREST ("the model as a distance field"); labels do not interpolate.  Output: the stored word (label |
+ *   votes << 16) if the voxel is valid and votes >= max(min_votes, 1), else 0.
+ *   vh_sample_labels_map: points in the camera frame; a point with .z == 0 gives 0, otherwise the point is moved by `pose`
+ *   with vh_sample_color_map's arithmetic and the rule above applies.  vh_raycast_labels is exactly vh_raycast_maps followed by
+ *   vh_sample_labels_map over its vertex map.
+ *   No label volume (or a context that holds an imported view): every output is 0, VH_OK.  The device calls only enqueue,
+ *   behind every queued frame; they allocate nothing and change nothing.  Argument checks are vh_sample_color's;
+ *   vh_sample_labels_host takes host buffers and synchronises.
+ * COUNTING.  vh_label_counts over the allocated blocks of `region` (NULL: the whole model; of this shard): for 1 <= l < n_bins
+ *   d_counts[l] = the valid voxels whose word has label l and votes >= max(min_votes, 1); d_counts[0] = the valid voxels
+ *   counted nowhere else (unlabelled, below min_votes, or a label >= n_bins), so the bins always sum to the valid voxels of
+ *   the region.  n_bins 1..65536; the call zeroes d_counts itself.  No label volume: everything goes to bin 0.  The call only
+ *   enqueues (its block list is the mesh's, whose scratch the first listing call allocates).
+ * REMOVING.  vh_remove_label: every voxel of the region's blocks whose word has `label` (1..65535) and votes >=
+ *   max(min_votes, 1) becomes {0, 0}, as a de-integrated voxel; its colour word, where a colour volume exists, becomes 0; its
+ *   label word becomes 0.  A block in which this pass cleared a voxel and whose 512 weights are then all == 0 is freed through
+ *   the deletion path of vh_delete_blocks, in a lock epoch of its own, exactly as vh_remove_components frees
+ *   (vh_counters.last_freed / freed_total; the compact list is left as vh_delete_blocks leaves it).  stats: the blocks listed,
+ *   the voxels cleared, the blocks freed.  The call synchronises.  VH_ERR_INVALID_ARGUMENT, with nothing changed: a context
+ *   that holds an imported view; a context without a label volume; a label outside 1..65535.
+ *   Limit: only voxels within `band` of the surface ever carry a label, so an object leaves the volume completely only if it
+ *   was labelled with band >= the truncation; with a thinner band the voxels between band and truncation stay, as a shell
+ *   without a zero crossing.
+ * KEEPING IT CONSISTENT.  A pool block that is not allocated has 512 zero label words: vh_delete_blocks, vh_garbage_collect,
+ *   vh_remove_components, vh_remove_label and vh_stream_out zero the label words of the blocks they free (so streaming a
+ *   block out drops its labels); vh_load_snapshot clears the volume.  vh_merge, vh_stream_out / vh_stream_in, vh_deintegrate*,
+ *   vh_changes' digest, snapshots, vh_save_color and view records neither carry nor read labels; carrying labels through them
+ *   is future work, as it was for colour.  After a plain de-integration the pairing is
+ *   vh_integrate_labels(old_pose, ..., vote_max = 0), which is the sweep.
+ *   vh_has_labels: 0 or 1.  vh_clear_labels zeroes the volume if there is one (enqueues only).  vh_download_labels
+ *   synchronises; VH_ERR_INVALID_ARGUMENT when there is no volume or the range is beyond it.
+ * Measured: nothing is promised; DESIGN.md 4.25 says what tools/labels_time.py printed, or that it has not run yet. */
+typedef struct vh_label_stats { uint64_t blocks, removed_voxels, freed_blocks; } vh_label_stats;
+
+int vh_integrate_labels(vh_context *ctx, const float pose[16], const uint16_t *d_depth, const float k_inv[9],
+                        const uint16_t *d_labels, float band, int32_t vote_max);
+int vh_integrate_labels_map(vh_context *ctx, const float pose[16], const vh_float4 *d_verts, const uint16_t *d_labels,
+                            float band, int32_t vote_max);
+int vh_has_labels(vh_context *ctx);
+int vh_clear_labels(vh_context *ctx);
+int vh_download_labels(vh_context *ctx, size_t first_voxel, uint32_t *host_dst, size_t count);   /* synchronises */
+int vh_sample_labels(vh_context *ctx, uint64_t n, const float *d_points /* n*3, world metres */, int32_t min_votes,
+                     uint32_t *d_words_out /* n words */);
+int vh_sample_labels_host(vh_context *ctx, uint64_t n, const float *h_points, int32_t min_votes, uint32_t *h_words_out);
+int vh_sample_labels_map(vh_context *ctx, const float pose[16], uint64_t n, const vh_float4 *d_points /* camera frame */,
+                         int32_t min_votes, uint32_t *d_words_out);
+int vh_raycast_labels(vh_context *ctx, const float pose[16], float t_min, float t_max, float *d_depth_out,
+                      vh_float4 *d_vertices_out, vh_float4 *d_normals_out, int32_t min_votes, uint32_t *d_words_out);
+int vh_label_counts(vh_context *ctx, const vh_mesh_region *region /* NULL: whole model */, int32_t min_votes,
+                    int32_t n_bins /* 1..65536 */, uint32_t *d_counts /* n_bins words */);
+int vh_label_counts_host(vh_context *ctx, const vh_mesh_region *region, int32_t min_votes, int32_t n_bins,
+                         uint32_t *h_counts);                                                    /* host buffer; synchronises */
+int vh_remove_label(vh_context *ctx, const vh_mesh_region *region /* NULL: whole model */, int32_t label /* 1..65535 */,
+                    int32_t min_votes, vh_label_stats *stats /* host, may be NULL */);
+
+/* ------------------------------------------------------------------ */
 /* incremental meshing: which blocks changed, and their triangles      */
 /* (tests/changes_ref.py is the rule in executable form) */
 /* ------------------------------------------------------------------ */

@@ -121,6 +121,14 @@ class ComponentStats(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class LabelStats(C.Structure):
+    """vh_label_stats."""
+    _fields_ = [(n, C.c_uint64) for n in ("blocks", "removed_voxels", "freed_blocks")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class PtrContainer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "d_heap", "d_hashTable", "d_compactifiedHashTable", "d_hashTableBucketMutex", "d_SDFBlocks",
@@ -221,6 +229,18 @@ SIGNATURES = {
     "vh_components_host": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, _vp, C.POINTER(_i32), C.POINTER(_i32), _vp,
                                      C.POINTER(ComponentStats)]),
     "vh_remove_components": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, C.POINTER(ComponentStats)]),
+    "vh_integrate_labels": (C.c_int, [_vp, _fp, _vp, _fp, _vp, _f, _i32]),
+    "vh_integrate_labels_map": (C.c_int, [_vp, _fp, _vp, _vp, _f, _i32]),
+    "vh_has_labels": (C.c_int, [_vp]),
+    "vh_clear_labels": (C.c_int, [_vp]),
+    "vh_download_labels": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t]),
+    "vh_sample_labels": (C.c_int, [_vp, C.c_uint64, _vp, _i32, _vp]),
+    "vh_sample_labels_host": (C.c_int, [_vp, C.c_uint64, _fp, _i32, C.POINTER(_u32)]),
+    "vh_sample_labels_map": (C.c_int, [_vp, _fp, C.c_uint64, _vp, _i32, _vp]),
+    "vh_raycast_labels": (C.c_int, [_vp, _fp, _f, _f, _vp, _vp, _vp, _i32, _vp]),
+    "vh_label_counts": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, _vp]),
+    "vh_label_counts_host": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.POINTER(_u32)]),
+    "vh_remove_label": (C.c_int, [_vp, C.POINTER(MeshRegion), _i32, _i32, C.POINTER(LabelStats)]),
     "vh_changes_state_bytes": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "vh_changes": (C.c_int, [_vp, _vp, C.POINTER(MeshRegion), _i32, _i32, C.c_uint64, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64),
                              C.POINTER(C.c_uint64)]),

@@ -276,6 +276,32 @@ void SDF_Hashtable::saveColor(const char *path) { check(vh_save_color(ctx_, path
 
 void SDF_Hashtable::loadColor(const char *path) { check(vh_load_color(ctx_, path), "loadColor"); }
 
+void SDF_Hashtable::integrateLabels(const float4x4 &pose, const uint16_t *d_depth, const float kInv[9], const uint16_t *d_labels,
+                                    float band, int voteMax)
+{
+    check(vh_integrate_labels(ctx_, pose.entries, d_depth, kInv, d_labels, band, voteMax), "integrateLabels");
+}
+
+void SDF_Hashtable::sampleLabels(const std::vector<float> &points, std::vector<uint32_t> &words, int minVotes)
+{
+    const uint64_t n = points.size() / 3;
+    words.assign((size_t)n, 0u);
+    check(vh_sample_labels_host(ctx_, n, points.data(), minVotes, words.data()), "sampleLabels");
+}
+
+void SDF_Hashtable::labelCounts(int nBins, std::vector<uint32_t> &counts, const vh_mesh_region *region, int minVotes)
+{
+    counts.assign(nBins > 0 ? (size_t)nBins : 0, 0u);
+    check(vh_label_counts_host(ctx_, region, minVotes, nBins, counts.data()), "labelCounts");
+}
+
+vh_label_stats SDF_Hashtable::removeLabel(int label, int minVotes, const vh_mesh_region *region)
+{
+    vh_label_stats st{};
+    check(vh_remove_label(ctx_, region, label, minVotes, &st), "removeLabel");
+    return st;
+}
+
 uint64_t SDF_Hashtable::streamOut(const vh_stream_region &region, std::vector<vh_view_record> &records, std::vector<uint32_t> *colors)
 {
     uint64_t selected = 0, written = 0;

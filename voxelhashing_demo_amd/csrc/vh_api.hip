@@ -183,6 +183,12 @@ struct ChangesScratch {
     DevBuf<unsigned long long> hostFirst;
 };
 
+// vh_remove_label (vh_api_labels.hip): scratch of the first call, kept and grown on demand
+struct LabelScratch {
+    DevBuf<int4> keys;                     // the keys of the blocks that emptied
+    DevBuf<unsigned long long> words;      // LabelWord[]: the counts of the call
+};
+
 struct vh_context {
     HashTableParams params;
     FrameParams fp;
@@ -274,6 +280,8 @@ struct vh_context {
     StreamScratch streaming;               // vh_stream_in, vh_stream_*_host: scratch of the first call, kept
     ComponentScratch components;           // vh_components, vh_remove_components: scratch of the first call, kept
     ChangesScratch changes;                // vh_changes, vh_extract_mesh_blocks: scratch of the first call, kept
+    DevBuf<uint32_t> labels;               // the label volume (vh_api_labels.hip): one word per voxel, of the first label-fusing call, kept
+    LabelScratch labelScratch;             // vh_remove_label: scratch of its first call, kept
 };
 
 // a scratch buffer (a DevBuf the context keeps) of at least `count` elements; what still uses a smaller one is synchronised away first
@@ -414,6 +422,8 @@ static int settle(vh_context *c);              // ... and folds a two-ended comp
 static int ensure_color(vh_context *c);        // vh_api_color.hip: the colour volume, allocated and zeroed if the context has none (all or nothing)
 static int release_color(vh_context *c);       // vh_api_color.hip: the colour words of the blocks a deletion freed, if there is a colour volume
 static hipError_t reset_color(vh_context *c);  // ... and the whole volume back to "no colour"
+static int release_labels(vh_context *c);      // vh_api_labels.hip: the same two for the label volume
+static hipError_t reset_labels(vh_context *c);
 static DevPtrs model_ptrs(const vh_context *c);    // vh_api_blocklist.hip: c->dp, with a view table's voxels where they live, in the records
 
 static int create_impl(const vh_config *cfg, uint32_t lo, uint32_t hi, vh_context **out)
@@ -663,3 +673,4 @@ static int ensure_band_candidates(vh_context *c)
 #include "vh_api_stream.hip"
 #include "vh_api_components.hip"
 #include "vh_api_changes.hip"
+#include "vh_api_labels.hip"

@@ -15,6 +15,7 @@ static int sweep_and_release(vh_context *c)
     }
     if (rc != VH_OK) return rc;
     rc = release_color(c);                           // (reads the freed list the release consumes)
+    if (rc == VH_OK) rc = release_labels(c);
     if (rc != VH_OK) return rc;
     rc = launch(c, kPhaseGc, gc_release_kernel, dim3(1024), dim3(256), c->dp);
     if (rc != VH_OK) return rc;
@@ -363,6 +364,7 @@ extern "C" int vh_load_snapshot(vh_context *c, const char *path)
     { const int frc = flush_pending(c); if (frc != VH_OK) return frc; }
     hipError_t e = reset_model(c);
     if (e == hipSuccess) e = reset_color(c);         // ptrs are re-dealt and the file carries no colour
+    if (e == hipSuccess) e = reset_labels(c);        // ... and no labels
     const size_t words = ((size_t)c->ownedBuckets + 31) / 32;
     std::vector<uint32_t> bits(words, 0u), macro(kMacroBits / 32, 0u);
     std::vector<Voxel> block(kBlockVoxels);

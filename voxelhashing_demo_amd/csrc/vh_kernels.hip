@@ -38,6 +38,10 @@
 //   vh_color.hip       the model in colour: a second volume of one word per voxel, the registered colour image fused into the
 //                      voxels near the surface in the TSDF update's launch shape and taken back out of them, colour at world
 //                      points with the sampler's shared look-ups (no counterpart in the reference)
+//   vh_labels.hip      the model with labels: a third volume of one word per voxel, a segmentation's label image fused into the
+//                      voxels near the surface as Boyer-Moore votes in colour's launch shape, labels at world points, valid voxels
+//                      per label with wave-aggregated atomics, one label taken out of the volume through the deletion path (no
+//                      counterpart in the reference)
 //   vh_stream.hip     block streaming: the blocks of a region out of the model as records (ordered list, pack, the deletion
 //                      path) and records back in (classification, the bin insertion path, one placed record per key); no
 //                      counterpart in the reference
@@ -76,6 +80,7 @@
 #include "vh_track.hip"
 #include "vh_merge.hip"
 #include "vh_color.hip"
+#include "vh_labels.hip"
 #include "vh_stream.hip"
 #include "vh_components.hip"
 #include "vh_changes.hip"

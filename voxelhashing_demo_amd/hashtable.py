@@ -348,6 +348,110 @@ class SDFHashtable:
                                            _dev_ptr(rgba)), "vh_raycast_color")
         return depth, verts, nrm, rgba
 
+    # ---- the model with labels ----
+    def _check_label_image(self, labels_u16, what):
+        if not isinstance(labels_u16, int):
+            if labels_u16.element_size() != 2 or labels_u16.is_floating_point():
+                raise ValueError(f"{what}: the label image must hold one 16-bit label per pixel (0: not labelled)")
+            if labels_u16.numel() != self.width * self.height:
+                raise ValueError(f"{what}: the label image must hold height * width pixels")
+            if not labels_u16.is_cuda:
+                raise ValueError(f"{what}: the label image must be a CUDA tensor")
+
+    def integrate_labels(self, pose, depth_u16, k_inv, labels_u16, band: float, vote_max: int = 65535):
+        """Asynchronous: the label image `labels_u16` [H, W] (uint16 or int16 storage, registered to the uint16 depth image; 0 =
+        not labelled) cast as one Boyer-Moore vote into every voxel within `band` metres of the surface, over the blocks `pose`
+        sees.  vote_max: 1..65535, the cap of a voxel's vote count; 0 only sweeps the labels of voxels that hold nothing (the
+        pairing after a de-integration).  The first call allocates the label volume."""
+        _, pp = _pose16(pose)
+        self._check_depth_u16(depth_u16, "integrate_labels")
+        self._check_label_image(labels_u16, "integrate_labels")
+        k = np.ascontiguousarray(np.asarray(k_inv, np.float32).reshape(9))
+        L.check(self._lib.vh_integrate_labels(self._h, pp, _dev_ptr(depth_u16), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                              _dev_ptr(labels_u16), float(band), int(vote_max)), "vh_integrate_labels")
+
+    def integrate_labels_map(self, pose, verts, labels_u16, band: float, vote_max: int = 65535):
+        """integrate_labels with the depth taken from the .z of a float4 vertex map [H, W, 4]."""
+        _, pp = _pose16(pose)
+        self._check_verts(verts, "integrate_labels_map")
+        self._check_label_image(labels_u16, "integrate_labels_map")
+        L.check(self._lib.vh_integrate_labels_map(self._h, pp, _dev_ptr(verts), _dev_ptr(labels_u16), float(band), int(vote_max)),
+                "vh_integrate_labels_map")
+
+    def has_labels(self) -> bool:
+        return bool(self._lib.vh_has_labels(self._h))
+
+    def clear_labels(self):
+        L.check(self._lib.vh_clear_labels(self._h), "vh_clear_labels")
+
+    def label_volume(self) -> np.ndarray:
+        """The label words of the whole volume (uint32, label | votes << 16; 0 = no label), indexed like sdf_blocks().  Raises
+        when the context has no label volume."""
+        out = np.empty(self.params.numVoxelBlocks * 512, np.uint32)
+        L.check(self._lib.vh_download_labels(self._h, 0, out.ctypes.data_as(C.c_void_p), out.size), "vh_download_labels")
+        return out
+
+    def sample_labels_into(self, points, words, min_votes: int = 1, n: int = None):
+        """vh_sample_labels into a caller-owned device buffer: points [n, 3] float32 (world metres), words [n] 32-bit words
+        (label | votes << 16 of the nearest voxel; 0 = no label, or fewer than min_votes votes).  Asynchronous."""
+        n = int(points.shape[0]) if n is None else int(n)
+        L.check(self._lib.vh_sample_labels(self._h, n, _dev_ptr(points), int(min_votes), _dev_ptr(words)), "vh_sample_labels")
+        return words
+
+    def sample_labels(self, points, min_votes: int = 1):
+        """The label words at world points [n, 3] (float32 CUDA tensor) as a uint32 CUDA tensor [n]; word & 0xFFFF is the label."""
+        import torch
+        words = torch.empty((int(points.shape[0]),), dtype=torch.uint32, device=points.device)
+        return self.sample_labels_into(points, words, min_votes)
+
+    def sample_labels_map_into(self, pose, points4, words, min_votes: int = 1, n: int = None):
+        """vh_sample_labels_map: camera-frame float4 points [n, 4] (a vertex map; .z == 0: no point) moved by `pose`."""
+        _, pp = _pose16(pose)
+        n = int(points4.numel() // 4) if n is None else int(n)
+        L.check(self._lib.vh_sample_labels_map(self._h, pp, n, _dev_ptr(points4), int(min_votes), _dev_ptr(words)),
+                "vh_sample_labels_map")
+        return words
+
+    def render_labels(self, pose, t_min: float = 0.1, t_max: float = 5.0, min_votes: int = 1):
+        """The model seen from `pose` with its labels (vh_raycast_labels): (depth [H, W], vertices [H, W, 4], normals [H, W, 4],
+        words [H, W] uint32) as CUDA tensors; a pixel without a hit or without a label is 0."""
+        import torch
+        _, pp = _pose16(pose)
+        with torch.cuda.device(self.device_index()):
+            depth = torch.empty((self.height, self.width), dtype=torch.float32, device="cuda")
+            verts = torch.empty((self.height, self.width, 4), dtype=torch.float32, device="cuda")
+            nrm = torch.empty((self.height, self.width, 4), dtype=torch.float32, device="cuda")
+            words = torch.empty((self.height, self.width), dtype=torch.uint32, device="cuda")
+        L.check(self._lib.vh_raycast_labels(self._h, pp, t_min, t_max, _dev_ptr(depth), _dev_ptr(verts), _dev_ptr(nrm),
+                                            int(min_votes), _dev_ptr(words)), "vh_raycast_labels")
+        return depth, verts, nrm, words
+
+    def label_counts_into(self, counts, n_bins: int, region=None, min_votes: int = 1):
+        """vh_label_counts into a caller-owned device buffer of n_bins 32-bit words.  Asynchronous."""
+        if not isinstance(counts, int) and counts is not None and (counts.element_size() != 4 or counts.numel() < int(n_bins)):
+            raise ValueError("label_counts_into: counts must hold n_bins 32-bit words")
+        L.check(self._lib.vh_label_counts(self._h, self._mesh_region(region), int(min_votes), int(n_bins), _dev_ptr(counts)),
+                "vh_label_counts")
+        return counts
+
+    def label_counts(self, n_bins: int, region=None, min_votes: int = 1):
+        """The valid voxels of `region` (None: the whole model) per label as a uint32 CUDA tensor [n_bins]: bin l for
+        1 <= l < n_bins, bin 0 everything else (unlabelled, fewer than min_votes votes, a label >= n_bins).  Asynchronous."""
+        import torch
+        if not 1 <= int(n_bins) <= 65536:
+            raise ValueError("label_counts: n_bins must be 1..65536")
+        with torch.cuda.device(self.device_index()):
+            counts = torch.empty((int(n_bins),), dtype=torch.uint32, device="cuda")
+        return self.label_counts_into(counts, n_bins, region, min_votes)
+
+    def remove_label(self, label: int, min_votes: int = 1, region=None) -> dict:
+        """vh_remove_label: every voxel that carries `label` with at least min_votes votes is cleared out of the volume (voxel
+        {0, 0}, colour 0, label 0), and the blocks that emptied are freed.  Returns the stats as a dict.  Synchronises."""
+        st = L.LabelStats()
+        L.check(self._lib.vh_remove_label(self._h, self._mesh_region(region), int(label), int(min_votes), C.byref(st)),
+                "vh_remove_label")
+        return st.as_dict()
+
     def integrate_batch(self, poses, verts_list, normals_list=None):
         """len(poses) frames in len(poses) + 1 launches (pipelined frames, flushed at the end); equals
         integrate() frame by frame."""
@@ -540,12 +644,13 @@ class SDFHashtable:
         """(vertices, triangles) of the indexed mesh inside `region`, None = the whole model."""
         return self.extract_mesh_indexed_into(0, 0, None, None, None, region)
 
-    def extract_mesh_indexed(self, region=None, normals: bool = False, colors: bool = False):
+    def extract_mesh_indexed(self, region=None, normals: bool = False, colors: bool = False, labels: bool = False):
         """The mesh of extract_mesh() in indexed form, made on the GPU: (vertices [V, 3] float32, faces [T, 3] int32) and
         per-vertex normals [V, 3] with normals=True.  One vertex per cell edge with a sign change (never merged by position);
         vertices[faces] has the bits of extract_mesh(), triangle for triangle.  colors=True appends the per-vertex colour
         words [V] uint32 (r | g << 8 | b << 16 | 0xFF << 24; 0 = no colour; mesh_io.save_ply takes them as they are): the
-        trilinear colour sample at the vertex where it has one, else the nearest voxel's."""
+        trilinear colour sample at the vertex where it has one, else the nearest voxel's.  labels=True appends (last) the
+        per-vertex label words [V] uint32 (label | votes << 16; 0 = no label): the nearest voxel's, sample_labels()."""
         import torch
         nv, nt = self.mesh_counts(region)
         if nv > 2**31 - 1:
@@ -563,6 +668,8 @@ class SDFHashtable:
             tri = self.sample_color(pos, L.SAMPLE_TRILINEAR).cpu().numpy()
             near = self.sample_color(pos, L.SAMPLE_NEAREST).cpu().numpy()
             out += (np.where(tri != 0, tri, near),)
+        if labels:
+            out += (self.sample_labels(pos).cpu().numpy(),)
         return out
 
     # ---- incremental meshing ----
